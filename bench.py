@@ -2,23 +2,31 @@
 """Benchmark of the sparse-voxel segmentation hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--mode fwd|fwdbwd] [--workload ...] [--scenes S]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input per GPU: GPU voxelisation of
 a resident Waymo-shaped scene (~180 k float32 points, 0.1 m voxels, grid 1440x1440x64, i.e.
 configs/waymo_one_sweep.yaml = BASELINE.json configs[1]) followed by Segformer forward + loss +
 backward + SGD step (default mode fwdbwd = the metric "points/sec fwd+bwd"; gradients all-reduced
-over RCCL when N > 1).  The forward-only eval rate of the same scenes is timed in the same run and
-reported as `fwd_only` (mode fwd makes it the headline instead).  Scenes shard data-parallel: every rank processes its own scenes,
+over RCCL when N > 1); mode fwd times the forward-only eval of the same scenes instead.
+Scenes shard data-parallel: every rank processes its own scenes,
 `value` = points processed by all ranks / max-over-ranks wall time ("scaling": "weak").
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR then writes what the last
+timed step returned (DIR/<name>.npy, see dump_outputs); the inputs are seeded, so two builds can be compared output for
+output.  --full adds everything else the benchmark measures or checks, as listed below: with --full a training run also
+times the forward-only eval of the same scenes (`fwd_only`) and probes for host gaps (`idle`), --storage bf16 times its
+fp32 side too, and N > 1 times the step without the gradient exchange (`allreduce`).
 
 N > 1: either an outer launcher provides RANK / WORLD_SIZE (python -m torch.distributed.run ... bench.py --gpus N), or
 `python bench.py --gpus N` starts its own N ranks (tools/dist_train.sh:7-13 does the same for the reference) -- the
 parent spawns fresh children before it ever touches a GPU and relays rank 0's line.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+Prints ONE JSON line on rank 0 with the contract fields, plus with --full
   roofline     -- the dominant kernel (sparse-conv gather-GEMM): algorithmic bytes / live HIP-event time
   cpu_baseline -- the CPU oracle (port of the reference algorithm) timed on the host cores, N=1 only
-  parity       -- GPU path vs that oracle on the same sample: logits, voxel ids, rulebooks.
+  parity       -- GPU path vs that oracle on the same sample: logits, voxel ids, rulebooks
+  fp32_exact   -- the same training step with exact-fp32 products, timed in a child run.
 """
 import argparse
 import json
@@ -39,6 +47,8 @@ PMC_TRAFFIC_FILES = ("r05_pmc_conv_traffic.json", "r05_pmc_conv_traffic_dense2m.
                      "r04_pmc_conv_traffic_multi_sweeps.json", "r04_pmc_conv_traffic_spnet.json", "r03_pmc_conv_traffic.json", "r03_pmc_conv_traffic_dense2m.json", "r03_pmc_conv_traffic_cylinder.json",
                      "r03_pmc_conv_traffic_multi_sweeps.json", "r03_pmc_conv_traffic_spnet.json", "r02_pmc_conv_traffic.json")
 ATTENTION_REPORT = None  # filled by conv_roofline's instrumented forward
+LAYERS_JSON = os.path.join(ROOT, "bench_out", "bench_layers.json")  # per-layer conv timings of the last --full run
+DUMP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much
 
 WORKLOADS = {
     "one_sweep": "waymo_one_sweep (BASELINE configs[1])",
@@ -58,6 +68,30 @@ def lib_sha16():
         for blk in iter(lambda: f.read(1 << 20), b""):
             h.update(blk)
     return h.hexdigest()[:16]
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: every tensor of `outputs` (what one step returned to its caller) as out_dir/<name>.npy -- float64
+    stays float64, integers become float64, other floats float32.  When all of them together exceed DUMP_BYTES, every
+    array keeps the same share of its rows, drawn with a fixed seed (sorted); out_dir/<name>_rows.npy then holds the row
+    indices (float64)."""
+    arrays = {k: v.detach() for k, v in outputs.items() if torch.is_tensor(v)}
+    arrays = {k: v.double() if v.dtype == torch.float64 or not v.is_floating_point() else v.float() for k, v in arrays.items()}
+    nbytes = lambda v: v.numel() * v.element_size()  # noqa: E731
+    rowed = {k for k, v in arrays.items() if v.dim() > 0 and v.shape[0] > 1}
+    share = 1.0
+    if sum(nbytes(v) for v in arrays.values()) > DUMP_BYTES:  # the sampled rows and their float64 indices must fit
+        fixed = sum(nbytes(v) for k, v in arrays.items() if k not in rowed)
+        room = DUMP_BYTES - fixed - 2048 * len(arrays)  # (a generous 1 KiB per .npy header)
+        share = room / sum(nbytes(arrays[k]) + 8 * arrays[k].shape[0] for k in rowed)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        if share < 1.0 and k in rowed:
+            n = v.shape[0]
+            rows = np.sort(np.random.default_rng(0).choice(n, max(int(n * share), 1), replace=False))
+            np.save(os.path.join(out_dir, f"{k}_rows.npy"), rows.astype(np.float64))
+            v = v[torch.from_numpy(rows).to(v.device)]
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.cpu().numpy())
 
 
 def parse():
@@ -102,7 +136,18 @@ def parse():
     ap.add_argument("--cpu-points", type=int, default=-1,
                     help="points of the CPU-baseline / parity sample (0 = whole scene; default: whole scene, "
                          "150000 for dense2m and 30000 current-sweep rows for multi_sweeps so that the run stays within minutes)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: CPU baseline and parity against the "
+                         "oracle, the exact-fp32 child run, rooflines and per-layer timings (written to "
+                         f"{os.path.relpath(LAYERS_JSON, ROOT)}), fwd_only and the idle probe of a training run, the fp32 "
+                         "side of --storage bf16, the exchange cost of N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (float32 / float64, at most "
+                         f"{DUMP_BYTES // 10**6} MB in all: a fixed, seeded row sample of a larger output)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def conv_roofline(model, batch, dev):
@@ -381,7 +426,7 @@ def main():
     # logit parity + CPU baseline on the weights the run starts from (seed 0), before anything is timed
     baseline = None
     parity_sample = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # bounded samples (10-30 s of CPU work): the dense scene's first 150 k points; of a multi-sweep scene the first
         # 30 k current-sweep rows with their image features and twice as many history rows (the oracle's DeepFusion kNN is
         # a brute-force O(n^2) search: minutes on a whole sweep)
@@ -543,17 +588,21 @@ def main():
         loss.backward()
         opt.step()
         prefetch(i)
-        return res
+        out = dict(res)
+        out["loss"] = loss
+        return out
 
     local_sec = {}
+    last = {}  # what the last timed step of each loop returned
 
     def timed(step_fn, tag):
         for i in range(args.warmup):
             step_fn(i)
         D.job_barrier(dev)
         t0 = time.perf_counter()
-        for i in range(args.steps):
+        for i in range(args.steps - 1):
             step_fn(args.warmup + i)
+        last[tag] = step_fn(args.warmup + args.steps - 1)
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         local_sec[tag] = time.perf_counter() - t0  # this rank alone (the job's time below adds the wait for the slowest)
@@ -641,18 +690,23 @@ def main():
     if train:
         net.train()
         if args.storage == "bf16" and dev.type == "cuda":
-            # the same steps with the fp32 copies first (same process, same box), then with the opt-in bf16 copies: the
-            # headline `value` of a --storage bf16 line is the second
-            torch.cuda.reset_peak_memory_stats(dev)
-            dt32, n32 = timed(train_step, "train_fp32_copies")
-            train_storage = {"ms_per_step_fp32_copies": round(dt32 / args.steps * 1e3, 3),
-                             "peak_memory_gb_fp32_copies": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 3)}
+            if args.full:
+                # the same steps with the fp32 copies first (same process, same box), then with the opt-in bf16 copies:
+                # the headline `value` of a --storage bf16 line is the second
+                torch.cuda.reset_peak_memory_stats(dev)
+                dt32, n32 = timed(train_step, "train_fp32_copies")
+                last.clear()
+                train_storage = {"ms_per_step_fp32_copies": round(dt32 / args.steps * 1e3, 3),
+                                 "peak_memory_gb_fp32_copies": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 3)}
             _ops.TRAIN_STORAGE = "bf16"
         if dev.type == "cuda":
             torch.cuda.reset_peak_memory_stats(dev)
         dt, n_pts = timed(train_step, "train")
         if dev.type == "cuda":
             peak_bytes = torch.cuda.max_memory_allocated(dev)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(last["train"], args.dump_outputs)
+        last.clear()
         if train_storage is not None:
             train_storage.update({"ms_per_step": round(dt / args.steps * 1e3, 3), "peak_memory_gb": round(peak_bytes / 2 ** 30, 3),
                                   "mode": "bf16 COPIES of the rows each sparse-conv / Linear weight gradient multiplies with are "
@@ -666,11 +720,11 @@ def main():
         # digit (SEG3D_WGRAD_STREAM=0 / --no-pipeline give the single-stream reference); under DDP every rank must hold
         # the same value
         weights_l1 = float(sum(p.detach().double().abs().sum() for p in model.parameters()))
-        if world == 1 and os.environ.get("SEG3D_BENCH_IDLE_PROBE", "1") != "0":
+        if args.full and world == 1 and os.environ.get("SEG3D_BENCH_IDLE_PROBE", "1") != "0":
             k_idle = min(max(args.steps, 1), 6)
             idle_report = idle_probe(args.warmup + args.steps, k_idle)
             extra_steps = 2 * k_idle + 1 if idle_report is not None else 0
-        if distributed and world > 1:
+        if args.full and distributed and world > 1:
             # what the gradient exchange costs on the critical path: the same steps with DDP's all-reduce switched off
             # (no_sync), after the fingerprint -- the ranks' weights diverge from here on, only eval timing follows
             k = min(args.steps, 5)
@@ -684,43 +738,55 @@ def main():
     net.eval()
     storage_report = None
     if args.storage == "bf16":
-        # the same weights, scene 0, both storages: what the opt-in mode costs in logits and what it buys in time
-        b_ref = B.batch_from_resident(resident[0], offsets[0], ds.voxel_size, ds.point_cloud_range, images[0], cyl)
-        with torch.no_grad():
-            ref_logits = model(b_ref)["point_out"].clone()
-        dt_f32, n_pts_f32 = timed(fwd_step, "fwd_fp32")
-        _ops.STORAGE = "bf16"
-        with torch.no_grad():
-            got = model(B.batch_from_resident(resident[0], offsets[0], ds.voxel_size, ds.point_cloud_range, images[0], cyl))["point_out"]
-        err = (got.float() - ref_logits).abs()
-        storage_report = {
-            "mode": "bf16 storage of the sparse-conv feature maps (inference forward; fp32 accumulate, bias and activation; "
-                    "residual stream, attention, norms and per-point MLPs stay fp32: tools/bf16_storage_probe.py)",
-            "vs_own_fp32_storage": {"max_abs_logit_diff": float(err.max()), "mean_abs_logit_diff": float(err.mean()),
-                                    "max_abs_logit": float(ref_logits.abs().max()),
-                                    "argmax_agreement": float((got.argmax(1) == ref_logits.argmax(1)).float().mean()),
-                                    "n_points": int(ref_logits.shape[0])},
-            "stated_tolerance": {"max_abs_logit_diff": 1e-1, "argmax_agreement": 0.99},
-            "fwd_ms_per_step_fp32_storage": round(dt_f32 / args.steps * 1e3, 3)}
-        del ref_logits, got
-    dt_f, n_pts_f = timed(fwd_step, "fwd")  # forward-only eval (BASELINE configs[1] as literally worded)
-    # (the instrumented passes below stay on the same stream: its allocator pool is warm, so no hipMalloc lands inside
-    # an event bracket -- the narrow-head layers of the dense scene once read 11 ms instead of 1.1 ms that way)
+        if args.full:
+            # the same weights, scene 0, both storages: what the opt-in mode costs in logits and what it buys in time
+            b_ref = B.batch_from_resident(resident[0], offsets[0], ds.voxel_size, ds.point_cloud_range, images[0], cyl)
+            with torch.no_grad():
+                ref_logits = model(b_ref)["point_out"].clone()
+            dt_f32, n_pts_f32 = timed(fwd_step, "fwd_fp32")
+            last.clear()
+            _ops.STORAGE = "bf16"
+            with torch.no_grad():
+                got = model(B.batch_from_resident(resident[0], offsets[0], ds.voxel_size, ds.point_cloud_range, images[0], cyl))["point_out"]
+            err = (got.float() - ref_logits).abs()
+            storage_report = {
+                "mode": "bf16 storage of the sparse-conv feature maps (inference forward; fp32 accumulate, bias and activation; "
+                        "residual stream, attention, norms and per-point MLPs stay fp32: tools/bf16_storage_probe.py)",
+                "vs_own_fp32_storage": {"max_abs_logit_diff": float(err.max()), "mean_abs_logit_diff": float(err.mean()),
+                                        "max_abs_logit": float(ref_logits.abs().max()),
+                                        "argmax_agreement": float((got.argmax(1) == ref_logits.argmax(1)).float().mean()),
+                                        "n_points": int(ref_logits.shape[0])},
+                "stated_tolerance": {"max_abs_logit_diff": 1e-1, "argmax_agreement": 0.99},
+                "fwd_ms_per_step_fp32_storage": round(dt_f32 / args.steps * 1e3, 3)}
+            del ref_logits, got
+        else:
+            _ops.STORAGE = "bf16"
+    dt_f = n_pts_f = None
+    if args.full or not train:
+        dt_f, n_pts_f = timed(fwd_step, "fwd")  # forward-only eval (BASELINE configs[1] as literally worded)
+        # (the instrumented passes below stay on the same stream: its allocator pool is warm, so no hipMalloc lands inside
+        # an event bracket -- the narrow-head layers of the dense scene once read 11 ms instead of 1.1 ms that way)
     if not train:
         dt, n_pts = dt_f, n_pts_f
+        if args.dump_outputs and rank == 0:
+            dump_outputs(last["fwd"], args.dump_outputs)
+    last.clear()
 
     rank_report = None
     if distributed:  # one record per rank: a scaling problem shows as one slow rank or as a large exchange share
         mine = {"rank": rank, "device": torch.cuda.get_device_name(dev) if dev.type == "cuda" else "cpu",
-                "ms_per_step": round(local_sec.get("train", local_sec["fwd"]) / args.steps * 1e3, 3),
-                "fwd_ms_per_step": round(local_sec["fwd"] / args.steps * 1e3, 3), "trained_weights_l1": weights_l1}
+                "ms_per_step": round(local_sec["train" if train else "fwd"] / args.steps * 1e3, 3),
+                "trained_weights_l1": weights_l1}
+        if "fwd" in local_sec:
+            mine["fwd_ms_per_step"] = round(local_sec["fwd"] / args.steps * 1e3, 3)
         rank_report = [None] * world
         dist.all_gather_object(rank_report, mine)
     out = None
     if rank == 0:
         model.eval()
         b0 = B.batch_from_resident(resident[0], offsets[0], ds.voxel_size, ds.point_cloud_range, images[0], cyl)
-        roof, per_layer = conv_roofline(model, b0, dev)
+        if args.full:
+            roof, per_layer = conv_roofline(model, b0, dev)
         if train:
             step_desc = ("fwd (attention dropout p=0.1, DropPath) + criterion (" + "+".join(cfg.MODEL.LOSSES)
                          + " on 3 heads) + bwd + SGD step")
@@ -747,12 +813,13 @@ def main():
                                    + ("batch i+1's voxelization and index plan on a third stream beside step i (same K "
                                       "voxelizations and plans inside the K timed steps)" if pipe_stream is not None
                                       else "every batch built at the start of its own step (--no-pipeline)"))},
-            "fwd_only": {"value": round(n_pts_f / dt_f, 1), "unit": "points/s",
-                         "ms_per_step": round(dt_f / args.steps * 1e3, 3)},
-            "roofline": roof,
-            "conv_layers": [{k: l[k] for k in ("rows", "cin", "cout", "us", "bound", "frac")} for l in per_layer],
-            "attention_roofline": ATTENTION_REPORT if args.segmentor == "segformer" else None,
         }
+        if dt_f is not None:
+            out["fwd_only"] = {"value": round(n_pts_f / dt_f, 1), "unit": "points/s", "ms_per_step": round(dt_f / args.steps * 1e3, 3)}
+        if args.full:
+            out["roofline"] = roof
+            out["conv_layers"] = [{k: l[k] for k in ("rows", "cin", "cout", "us", "bound", "frac")} for l in per_layer]
+            out["attention_roofline"] = ATTENTION_REPORT if args.segmentor == "segformer" else None
         if idle_report is not None:
             out["idle"] = idle_report
         if peak_bytes is not None:
@@ -775,11 +842,11 @@ def main():
                                             "same step under no_sync()"}
         # the attention temperature after the timed steps: below ~0.036 the kernels leave the fixed-maximum softmax
         taus = [float(p.detach()) for n, p in model.named_parameters() if n.endswith(".tau")]
-        if taus and out["attention_roofline"] is not None:
+        if taus and out.get("attention_roofline") is not None:
             out["attention_roofline"]["tau_range_after_steps"] = [round(min(taus), 4), round(max(taus), 4)]
         profiled = any(k in os.environ for k in ("ROCPROFILER_SDK_TOOL_LIBRARIES", "ROCP_TOOL_LIBRARIES", "ROCPROF_OUTPUT_PATH")) \
             or "rocprof" in os.environ.get("LD_PRELOAD", "")
-        if (train and world == 1 and not distributed and not profiled and not args.no_fp32_exact
+        if (args.full and train and world == 1 and not distributed and not profiled and not args.no_fp32_exact
                 and _ops.CONV_PRECISION == "bf16x3" and args.workload == "one_sweep" and args.segmentor == "segformer"):
             # the same step with every conv / Linear product an exact fp32 MFMA (the reference's arithmetic), in a fresh child
             # process (the switch is read at import): the same-precision number, driver-recorded
@@ -792,7 +859,8 @@ def main():
             env["SEG3D_CONV_PRECISION"] = "fp32"
             try:
                 child = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "5", "--warmup", "2", "--scenes", "2",
-                                        "--no-cpu-baseline", "--no-fp32-exact"], capture_output=True, text=True, timeout=600, env=env)
+                                        "--full", "--no-cpu-baseline", "--no-fp32-exact"], capture_output=True, text=True, timeout=600,
+                                       env=env)
                 fp32 = {"error": child.stderr[-300:]}
                 for line in child.stdout.splitlines():
                     if line.startswith("{"):
@@ -819,9 +887,10 @@ def main():
                 after = parity_report(*parity_sample, ds, model, dev, o_res, o_coords, o_ids)
                 out["parity"]["after_training"] = {k: after[k] for k in after if k.startswith("max_") or k.endswith("bit_exact")}
                 out["parity"]["after_training"]["steps"] = args.steps + args.warmup + extra_steps
-        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-        with open(os.path.join(ROOT, "gpurun_out", "bench_layers.json"), "w") as f:
-            json.dump(per_layer, f, indent=1)
+        if args.full:
+            os.makedirs(os.path.dirname(LAYERS_JSON), exist_ok=True)
+            with open(LAYERS_JSON, "w") as f:
+                json.dump(per_layer, f, indent=1)
         print(json.dumps(out), flush=True)
     if hi is not None:
         torch.cuda.default_stream(dev).wait_stream(hi)

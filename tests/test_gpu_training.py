@@ -90,7 +90,7 @@ def test_training_step_is_bit_reproducible(segmentor):
 
 def test_bench_prints_one_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--scenes", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -123,6 +123,36 @@ def test_bench_prints_one_contract_line():
                 "gpu_opt_step_ms_fed", "gpu_between_steps_ms", "host_in_prefetch_ms"):
         assert key in idle and idle[key] >= 0.0, key
     assert idle["gpu_step_ms_fed"] > 10.0 and idle["host_enqueue_ms"] > 1.0
+
+
+def test_plain_bench_run_times_only_the_steps_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the contract fields and none of the extra measurements; --steps sets the timed
+    steps; --dump-outputs writes what the last timed step returned (logits of the three heads, their coordinates, the
+    loss), and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--scenes", "1",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "points/s"
+        for key in ("roofline", "conv_layers", "attention_roofline", "fp32_exact", "idle", "fwd_only", "cpu_baseline", "parity"):
+            assert key not in line, key
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert {"point_out.npy", "voxel_out.npy", "aux_voxel_out.npy", "loss.npy"} <= set(files), sorted(files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 10**6
+        assert files["point_out.npy"].shape[1] == 22 and np.isfinite(files["point_out.npy"]).all()
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
 
 
 def test_bench_distributed_path_single_rank_rehearsal():
@@ -206,7 +236,7 @@ def test_full_size_configs_logits_match_oracle(workload, extra, n_expect):
     bit-exact, per-point logits within 1e-3 (the multi-sweep sample is the first 30 000 current-sweep rows + 15 000 rows of
     each of the four history sweeps: the oracle's brute-force kNN sets that limit, bench.py `n_cpu`)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--mode", "fwd", "--steps", "1",
-                          "--warmup", "1"] + extra, capture_output=True, text=True, timeout=1500, cwd=ROOT)
+                          "--warmup", "1", "--full"] + extra, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][-1])
     par = line["parity"]

@@ -329,3 +329,29 @@ def test_deferred_join_bookkeeping_is_safe_by_construction(monkeypatch):
     deferred, fk = log.pop()
     assert deferred and fk.main.waits == 1 and ran == [["inner sum"], ["outer sum"]] and not ops._DEFERRED
     assert torch.equal(w_out.grad, torch.full((4,), 2.0)) and torch.equal(w_in.grad, torch.full((4,), 2.0))
+
+
+def test_bench_output_dump_keeps_a_seeded_sample_within_its_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: small outputs are written whole; above the cap every array keeps the same seeded share of
+    its rows (indices beside it) and the files stay within the cap."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200_000)
+    g = torch.Generator().manual_seed(1)
+    outs = {"point_out": torch.randn(4000, 22, generator=g), "voxel_coords": torch.randint(0, 1440, (1500, 4), generator=g),
+            "loss": torch.tensor(0.5, dtype=torch.float64, requires_grad=True) * 2, "batch_size": 1}
+    bench.dump_outputs({"point_out": outs["point_out"][:100], "loss": outs["loss"]}, tmp_path / "small")
+    small = {f.name: np.load(f) for f in (tmp_path / "small").iterdir()}
+    assert sorted(small) == ["loss.npy", "point_out.npy"] and small["loss.npy"].dtype == np.float64
+    assert np.array_equal(small["point_out.npy"], outs["point_out"][:100].numpy())
+    for run in ("a", "b"):
+        bench.dump_outputs(outs, tmp_path / run)
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == ["loss.npy", "point_out.npy", "point_out_rows.npy", "voxel_coords.npy", "voxel_coords_rows.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 200_000
+    for name in files:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    rows = np.load(tmp_path / "a" / "point_out_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "point_out.npy"), outs["point_out"].numpy()[rows])
+    vc = np.load(tmp_path / "a" / "voxel_coords.npy")
+    assert vc.dtype == np.float64 and np.array_equal(vc, outs["voxel_coords"].numpy()[np.load(tmp_path / "a" / "voxel_coords_rows.npy").astype(np.int64)])

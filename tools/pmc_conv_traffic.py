@@ -1,5 +1,5 @@
 """Build profiles/rNN_pmc_conv_traffic.json from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of
-`bench.py --mode fwd --steps 2 --warmup 1 --no-cpu-baseline` and the per-layer list bench.py writes.
+`bench.py --full --mode fwd --steps 2 --warmup 1 --no-cpu-baseline` and the per-layer list such a run writes.
 
 usage: python tools/pmc_conv_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> <bench_layers.json> <out.json>
 Correction (MI355X_MICROARCH.md, HBM section): counter unit KiB; FETCH_SIZE counts 128-B read requests as 64 B on
@@ -44,7 +44,7 @@ def main():
         tot_t += traffic
         tot_a += algo
     doc = {"command": "rocprofv3 --pmc FETCH_SIZE | --pmc WRITE_SIZE (two separate passes) --output-format csv -- python3 "
-                      "bench.py --mode fwd --steps 2 --warmup 1 --no-cpu-baseline; tools/pmc_conv_traffic.py",
+                      "bench.py --full --mode fwd --steps 2 --warmup 1 --no-cpu-baseline; tools/pmc_conv_traffic.py",
            "correction": "gfx950: FETCH_SIZE counts 128-B read requests as 64 B -> doubled (MI355X_MICROARCH.md section "
                          "HBM); WRITE_SIZE taken as is; counter unit KiB",
            "kernel": f"spconv_tile_kernel<*> / spconv_split_kernel<*, 2, false> ({n} sparse-conv launches of the scene-0 forward)",

@@ -1,6 +1,6 @@
 # one-rank rehearsal of the data-parallel wrappers against the plain step, alternating on ONE box
 O=gpurun_out/r4ddp; mkdir -p $O
-B="bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-fp32-exact"
+B="bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-fp32-exact"
 for rep in 1 2; do
 python $B > $O/plain_$rep.json 2> $O/plain_$rep.err; echo plain rc=$?
 SEG3D_BENCH_DIST=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 $B > $O/native_$rep.json 2> $O/native_$rep.err; echo native rc=$?

@@ -1,6 +1,6 @@
 out=gpurun_out/r5r; mkdir -p $out
 for rep in 1 2 3; do for v in 0 1; do
-  SEG3D_BENCH_PIPE_THREAD=$v timeout -k 10 600 python bench.py --steps 15 --warmup 4 --no-cpu-baseline --no-fp32-exact > $out/bench_$v.json 2> $out/bench_$v.err || { tail -n 20 $out/bench_$v.err; exit 1; }
+  SEG3D_BENCH_PIPE_THREAD=$v timeout -k 10 600 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-fp32-exact > $out/bench_$v.json 2> $out/bench_$v.err || { tail -n 20 $out/bench_$v.err; exit 1; }
   python - <<PY
 import json
 d = json.loads([l for l in open("$out/bench_$v.json") if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_conv_
 tail -n 1 $out/parity.log
 SEG3D_CONV_XCD_RUN=1 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py -x -q -k "sparse_conv_forward_and_backward or inverse_conv or wide_tiles" > $out/parity_x1.log 2>&1 || { tail -n 30 $out/parity_x1.log; exit 1; }
 tail -n 1 $out/parity_x1.log
-timeout -k 10 900 python bench.py --workload dense2m --storage bf16 --steps 6 --warmup 2 --no-cpu-baseline > $out/dense2m_bf16.json 2> $out/dense2m_bf16.err || { tail -n 20 $out/dense2m_bf16.err; exit 1; }
+timeout -k 10 900 python bench.py --full --workload dense2m --storage bf16 --steps 6 --warmup 2 --no-cpu-baseline > $out/dense2m_bf16.json 2> $out/dense2m_bf16.err || { tail -n 20 $out/dense2m_bf16.err; exit 1; }
 python - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r5g/dense2m_bf16.json") if l.startswith("{")][-1])

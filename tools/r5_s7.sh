@@ -6,7 +6,7 @@ for rep in 1 2; do for b in 1 0; do
   echo "block env=$b: $(grep -v amdgpu $out/attn_b${b}_$rep.txt | tail -n 2 | tr '\n' ' ')"
 done; done
 for rep in 1 2; do for b in 1 0; do
-  SEG3D_ATTN_XCD_BLOCK=$b timeout -k 10 600 python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-fp32-exact > $out/bench_b${b}_$rep.json 2> $out/bench_b${b}_$rep.err || exit 1
+  SEG3D_ATTN_XCD_BLOCK=$b timeout -k 10 600 python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-fp32-exact > $out/bench_b${b}_$rep.json 2> $out/bench_b${b}_$rep.err || exit 1
   python - <<PY
 import json
 d = json.loads([l for l in open("$out/bench_b${b}_$rep.json") if l.startswith("{")][-1])

@@ -4,7 +4,7 @@ tail -n 1 $out/tests.log
 for rep in 1 2; do for v in 0 1; do SEG3D_LINEAR_COLGROUPS=$v timeout -k 10 300 python tools/linear_bench.py > $out/lin_$v.log 2>&1 || exit 1; done; done
 paste <(grep -v amdgpu $out/lin_0.log | awk '{print $2,$3,$4,$5,$7}') <(grep -v amdgpu $out/lin_1.log | awk '{print $7}')
 for rep in 1 2; do for v in 0 1; do
-  SEG3D_LINEAR_COLGROUPS=$v timeout -k 10 600 python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-fp32-exact > $out/bench_$v.json 2> $out/bench_$v.err || exit 1
+  SEG3D_LINEAR_COLGROUPS=$v timeout -k 10 600 python bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-fp32-exact > $out/bench_$v.json 2> $out/bench_$v.err || exit 1
   python - <<PY
 import json
 d = json.loads([l for l in open("$out/bench_$v.json") if l.startswith("{")][-1])
