@@ -665,6 +665,65 @@ int seg3d_lovasz_softmax_fwd(const float* logits, const int64_t* labels, int64_t
 int seg3d_lovasz_softmax_bwd(const float* logits, const float* coef, const float* stats, const float* grad_out,
                              int64_t n, int32_t c, float* dlogits, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Evaluation path (csrc/eval.hip): tools/eval.py:35-64 with --tta, test_time_aug.py:15-35 (MultiScaleFlipAug),
+ * seg3d/core/evaluation/iou_metric.py:21-53 (IOUMetric.fast_hist / add).  None of the three allocates.
+ *
+ * seg3d_tta_views_f32: the views of ONE frame (points [n, dim] float32, no batch column, 3 <= dim <= 16) written as
+ * collated rows out [n_views * n, 1 + dim], views in table order: column 0 = view index (v % batch_period when
+ * batch_period > 0, so that a slice of K consecutive views is a batch 0..K-1 when batch_period = K), then per point, in
+ * float32 without fused multiply-add, the reference's recipe (test_time_aug.py:26-31, transform_utils.py:11-32):
+ *   xyz *= scale;  x' = x*cos + y*(-sin);  y' = x*sin + y*cos;  z unchanged;  flip_x: y' = -y';  flip_y: x' = -x'
+ * and the other columns copied.  cos / sin are the caller's float32 constants (the reference takes torch.cos / torch.sin
+ * of the float32 angle).  `table` is a HOST pointer; the kernel receives the table by value among its arguments.
+ * n_views in [1, 64], flips 0 / 1, n_views * n <= INT32_MAX: SEG3D_EINVAL otherwise.
+ * seg3d_tta_views_host_f32: the same contract on HOST pointers, plain C++ (no HIP call, runs without a GPU context, as
+ * seg3d_voxelize_host_f32 does); bit-identical to the device kernel.
+ */
+#define SEG3D_TTA_MAX_VIEWS 64
+typedef struct {
+  float scale, cos_a, sin_a;
+  int32_t flip_x, flip_y; /* 0 / 1 */
+} seg3d_tta_view;
+typedef struct {
+  int32_t n_views;
+  int32_t batch_period; /* 0 = column 0 holds the view index itself */
+  seg3d_tta_view views[SEG3D_TTA_MAX_VIEWS];
+} seg3d_tta_table;
+int seg3d_tta_views_f32(const float* points, int64_t n_points, int32_t dim, const seg3d_tta_table* table, float* out,
+                        void* stream);
+int seg3d_tta_views_host_f32(const float* points, int64_t n_points, int32_t dim, const seg3d_tta_table* table,
+                             float* out);
+
+/* seg3d_softmax_accumulate_f32: logits [n_views * n_points, c] of one forward over n_views consecutive views (view-major,
+ * as seg3d_tta_views_f32 lays them out), acc [n_points, c] float32.  Per point, view by view in order:
+ *   m = max_c l;  e_c = expf(l_c - m);  s = sum_c e_c (fixed c order);  p_c = e_c / s (correctly rounded);
+ *   acc_c = acc_c + p_c  (first = 1: the first view of this call overwrites acc instead)
+ * -- F.softmax(point_out, dim=1) per view (eval.py:49) and the running sum behind torch.stack + torch.mean (:51-52).
+ * One rounded add per view in view order: for the same logits the result is bit-identical however the views are split
+ * into calls.  n_views in [1, 64], 1 <= c <= 64, n_views * n_points <= INT32_MAX.
+ */
+int seg3d_softmax_accumulate_f32(const float* logits, int64_t n_points, int32_t n_views, int32_t c, int32_t first,
+                                 float* acc, void* stream);
+
+/* seg3d_argmax_confusion: eval.py:55-58 (torch.argmax of point_out or of the mean probabilities) + IOUMetric.add
+ * (iou_metric.py:21-37, 50-56) on the device.  Predictions come from exactly one of
+ *   scores  [n, c] float32: pred = argmax_c score; with n_views > 0 the argmax is taken of score / n_views (the
+ *           correctly rounded quotient torch.mean forms, not a product with 1/n_views: two distinct sums may tie);
+ *           ties: the first maximum wins; NaN counts as the maximum and the first NaN wins (torch.argmax's rule)
+ *   pred_in [n] int64: predictions already made ("labels in, hist out"; pred and n_views must then be 0 / NULL)
+ * pred  nullable out [n] int64;
+ * hist  nullable in/out int64 [c * c], hist[gt * c + pred] += 1, ACCUMULATED (never cleared here); needs labels:
+ *       labels [n] uint8 (label_bytes 1, as the loader delivers them) or int64 (label_bytes 8, after load_data_to_gpu);
+ *       labels outside [0, c) -- the ignore index 255 among them -- are skipped (iou_metric.py:33), as are predictions
+ *       outside [0, c).  Per-workgroup LDS histogram of 32-bit counters, one 64-bit atomic per non-zero bin: integer-
+ *       exact and independent of the order of the points.
+ * 1 <= c <= 64 (SEG3D_EINVAL above), at least one of pred / hist.
+ */
+#define SEG3D_ARGMAX_MAX_CLASSES 64
+int seg3d_argmax_confusion(const float* scores, const int64_t* pred_in, int64_t n_points, int32_t c, int32_t n_views,
+                           const void* labels, int32_t label_bytes, int64_t* pred, int64_t* hist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 40
+ABI_VERSION = 41
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -122,6 +122,10 @@ SIGNATURES = {
     "seg3d_class_context_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f, _p, _p, _p, _p]),
     "seg3d_knn_attention_fwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _f, _p, _p, _p]),
     "seg3d_knn_attention_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _f, _p, _p, _p, _p, _p]),
+    "seg3d_tta_views_f32": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _p]),
+    "seg3d_tta_views_host_f32": (ctypes.c_int, [_p, _i64, _i32, _p, _p]),
+    "seg3d_softmax_accumulate_f32": (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p]),
+    "seg3d_argmax_confusion": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _p, _i32, _p, _p, _p]),
 }
 
 _ERR = {EINVAL: "SEG3D_EINVAL (bad argument)", EWORKSPACE: "SEG3D_EWORKSPACE (workspace too small)",

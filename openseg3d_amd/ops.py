@@ -13,6 +13,7 @@ import ctypes
 import weakref
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2349,3 +2350,109 @@ def lovasz_softmax(logits, labels, ignore_index=255, classes="present", class_we
     if class_weight is not None:
         class_weight = _f32c(torch.as_tensor(class_weight, dtype=torch.float32, device=logits.device))
     return _LovaszSoftmaxFn.apply(logits, labels, ignore_index, mode, include, class_weight)
+
+
+# ------------------------------------------------------------------------------------------ evaluation (csrc/eval.hip)
+class TtaView(ctypes.Structure):
+    _fields_ = [("scale", ctypes.c_float), ("cos_a", ctypes.c_float), ("sin_a", ctypes.c_float),
+                ("flip_x", ctypes.c_int32), ("flip_y", ctypes.c_int32)]
+
+
+TTA_MAX_VIEWS = 64
+
+
+class TtaTable(ctypes.Structure):
+    """seg3d_tta_table (include/seg3d_hip.h): up to 64 views {scale, cos, sin, flip_x, flip_y}."""
+    _fields_ = [("n_views", ctypes.c_int32), ("batch_period", ctypes.c_int32), ("views", TtaView * TTA_MAX_VIEWS)]
+
+
+def tta_table(scales, angles, flip_x, flip_y, batch_period=0):
+    """The views of MultiScaleFlipAug in the reference's loop order (test_time_aug.py:18-21): scale outermost, then angle,
+    then flip_x in [True, False], then flip_y in [True, False] ([False] for a flag that is off, :12-13; a list is taken
+    as given, as MultiScaleFlipAug stores it).  cos / sin are
+    computed as transform_utils.py:18-22 does: the angle cast to float32, torch.cos / torch.sin on the CPU."""
+    fx = list(flip_x) if isinstance(flip_x, (list, tuple)) else ([True, False] if flip_x else [False])
+    fy = list(flip_y) if isinstance(flip_y, (list, tuple)) else ([True, False] if flip_y else [False])
+    views = [(s, a, x, y) for s in scales for a in angles for x in fx for y in fy]
+    if not 1 <= len(views) <= TTA_MAX_VIEWS:
+        raise ValueError(f"{len(views)} test-time views: the kernels take 1 .. {TTA_MAX_VIEWS}")
+    ang = torch.tensor([float(a) for _, a, _, _ in views], dtype=torch.float32)
+    cos, sin = torch.cos(ang).tolist(), torch.sin(ang).tolist()
+    t = TtaTable()
+    t.n_views, t.batch_period = len(views), int(batch_period)
+    for v, (s, _, x, y) in enumerate(views):
+        # numpy's `points[:, :3] *= scale` on float32 rows multiplies by float32(scale) (test_time_aug.py:26)
+        t.views[v] = TtaView(float(np.float32(s)), cos[v], sin[v], int(bool(x)), int(bool(y)))
+    return t
+
+
+def tta_views(points, table):
+    """seg3d_tta_views_f32: one frame's float32 [N, D] CUDA points -> [V * N, 1 + D] collated rows, one launch."""
+    _need_gpu(points)
+    if points.dim() != 2 or points.dtype != torch.float32:
+        raise _lib.Seg3dError("points must be a float32 [N, D] tensor")
+    points = points.contiguous()
+    n, d = points.shape
+    out = torch.empty((table.n_views * n, d + 1), dtype=torch.float32, device=points.device)
+    _lib.call("seg3d_tta_views_f32", _ptr(points), n, d, ctypes.byref(table), _ptr(out), _stream())
+    return out
+
+
+def tta_views_host(points, table):
+    """seg3d_tta_views_host_f32: the same views on the host (numpy float32 [N, D] -> [V * N, 1 + D]); no HIP call."""
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    if pts.ndim != 2:
+        raise _lib.Seg3dError("points must be a float32 [N, D] array")
+    n, d = pts.shape
+    out = np.empty((table.n_views * n, d + 1), dtype=np.float32)
+    _lib.call("seg3d_tta_views_host_f32", ctypes.c_void_p(pts.ctypes.data), n, d, ctypes.byref(table),
+              ctypes.c_void_p(out.ctypes.data))
+    return out
+
+
+def softmax_accumulate(logits, acc, first):
+    """seg3d_softmax_accumulate_f32: acc [N, C] (+)= softmax of each of the K views in logits [K * N, C], view by view."""
+    _need_gpu(logits, acc)
+    if logits.dtype != torch.float32 or acc.dtype != torch.float32 or not acc.is_contiguous() or acc.dim() != 2 \
+            or logits.dim() != 2 or logits.shape[1] != acc.shape[1] or (acc.shape[0] and logits.shape[0] % acc.shape[0]):
+        raise _lib.Seg3dError("softmax_accumulate: float32 logits [K*N, C] and a contiguous float32 accumulator [N, C]")
+    n, c = acc.shape
+    k = logits.shape[0] // n if n else 1
+    _lib.call("seg3d_softmax_accumulate_f32", _ptr(logits.contiguous()), n, k, c, int(bool(first)), _ptr(acc), _stream())
+    return acc
+
+
+def argmax_confusion(scores=None, n_classes=None, pred_in=None, labels=None, hist=None, n_views=0, want_pred=True):
+    """seg3d_argmax_confusion.  Predictions from scores [N, C] (argmax; of scores / n_views when n_views > 0) or given as
+    pred_in [N] int64; labels uint8 / int64 [N] (nullable), hist int64 [C * C] accumulated in place (nullable).  Returns
+    pred int64 [N] (None when want_pred is False or pred_in is given)."""
+    src = scores if scores is not None else pred_in
+    _need_gpu(src, labels, hist)
+    c = int(scores.shape[1]) if scores is not None else int(n_classes)
+    n = int(src.shape[0])
+    if scores is not None:
+        if scores.dtype != torch.float32 or scores.dim() != 2:
+            raise _lib.Seg3dError("scores must be a float32 [N, C] tensor")
+        scores = scores.contiguous()
+    if pred_in is not None:
+        pred_in = pred_in.contiguous() if pred_in.dtype == torch.int64 else pred_in.long().contiguous()
+    lb = 0
+    if labels is not None:
+        if labels.dtype == torch.uint8:
+            lb = 1
+        elif labels.dtype == torch.int64:
+            lb = 8
+        else:
+            labels = labels.long()
+            lb = 8
+        labels = labels.contiguous()
+        if labels.numel() != n:
+            raise _lib.Seg3dError(f"{labels.numel()} labels for {n} points")
+    if hist is not None and labels is None:
+        raise _lib.Seg3dError("a confusion matrix needs labels")
+    if hist is not None and (hist.dtype != torch.int64 or not hist.is_contiguous() or hist.numel() != c * c):
+        raise _lib.Seg3dError(f"hist must be a contiguous int64 tensor of {c * c} counters")
+    pred = torch.empty((n,), dtype=torch.int64, device=src.device) if want_pred and pred_in is None else None
+    _lib.call("seg3d_argmax_confusion", _ptr(scores), _ptr(pred_in), n, c, int(n_views), _ptr(labels), lb, _ptr(pred),
+              _ptr(hist), _stream())
+    return pred
