@@ -73,6 +73,33 @@ def test_host_only_entry_points():
     # both weight-gradient kernels fit the workspace the query reports; the opt-in switch validates its argument
     assert _lib.query("seg3d_linear_wgrad_workspace_bytes", 58453, 192, 192) >= 8 * (192 * 192 + 192) * 4
     assert _lib.load().seg3d_debug_set_wgrad_lds(2) == _lib.EINVAL and _lib.load().seg3d_debug_set_wgrad_lds(-1) == 0
+    # weight-gradient argument checks: every case below returns before a launch (the non-null addresses are never read)
+    lib, fake, chunks = _lib.load(), ctypes.c_void_p(256), ctypes.c_int32(7)
+    big = 1 << 40
+    for name in ("seg3d_spconv_wgrad_partials", "seg3d_spconv_wgrad_partials_xbf16"):
+        f = getattr(lib, name)
+        for cin, cout in ((24, 32), (32, 40), (8, 16), (0, 16)):
+            assert f(fake, fake, fake, 100, 100, cin, cout, fake, big, ctypes.byref(chunks), None) == _lib.EINVAL, (name, cin, cout)
+        chunks.value = 7
+        assert f(None, None, None, 0, 0, 32, 32, None, 0, ctypes.byref(chunks), None) == 0 and chunks.value == 0, name
+        need = _lib.query("seg3d_spconv_wgrad_workspace_bytes", 1000, 32, 64)
+        assert need >= 27 * 32 * 64 * 4
+        assert f(fake, fake, fake, 1000, 1000, 32, 64, fake, need - 4, ctypes.byref(chunks), None) == _lib.EINVAL, name
+        assert f(fake, fake, fake, 1000, 1000, 32, 64, None, need, ctypes.byref(chunks), None) == _lib.EINVAL, name
+    assert lib.seg3d_spconv_wgrad(fake, fake, fake, 100, 100, 24, 32, 4, fake, fake, big, None) == _lib.EINVAL
+    need = _lib.query("seg3d_spconv_wgrad_workspace_bytes", 1000, 48, 48)
+    assert lib.seg3d_spconv_wgrad(fake, fake, fake, 1000, 1000, 48, 48, 4, fake, fake, need - 4, None) == _lib.EINVAL
+    for name in ("seg3d_linear_wgrad_partials", "seg3d_linear_wgrad_partials_xbf16"):
+        f = getattr(lib, name)
+        for cin, cout in ((6, 64), (64, 22), (0, 16)):
+            assert f(fake, fake, 100, cin, cout, 1, fake, big, ctypes.byref(chunks), None) == _lib.EINVAL, (name, cin, cout)
+        chunks.value = 7
+        need0 = _lib.query("seg3d_linear_wgrad_workspace_bytes", 0, 12, 40)
+        assert f(None, None, 0, 12, 40, 1, None, need0, ctypes.byref(chunks), None) == 0 and chunks.value == 0, name
+        need = _lib.query("seg3d_linear_wgrad_workspace_bytes", 70001, 12, 40)
+        assert need >= 8 * (12 * 40 + 40) * 4
+        assert f(fake, fake, 70001, 12, 40, 1, fake, need - 4, ctypes.byref(chunks), None) == _lib.EINVAL, name
+    assert lib.seg3d_linear_wgrad(fake, fake, 100, 6, 64, fake, None, fake, big, None) == _lib.EINVAL
 
 
 @pytest.mark.parametrize("tag,rng,vs", [("cart", [-72, -72, -2, 72, 72, 4.4], [0.1, 0.1, 0.1]),

@@ -5,12 +5,17 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("m,cin,cout", [(1000, 48, 96), (4097, 64, 64), (31, 192, 384), (70000, 96, 192),
-                                        (513, 104, 48), (5000, 256, 64), (64, 768, 384),
-                                        # the wide kernel's block shapes: 2 x 3, 3 x 2, 2 x 2 waves, ragged last steps
-                                        (40001, 192, 384), (33333, 384, 192), (20011, 384, 384), (9999, 384, 768),
-                                        (20000, 768, 384), (12345, 128, 256)])
-def test_linear_wgrad_matches_autograd(m, cin, cout):
+_WGRAD_SHAPES = [(1000, 48, 96), (4097, 64, 64), (31, 192, 384), (70000, 96, 192), (513, 104, 48), (5000, 256, 64), (64, 768, 384),
+                 # the wide kernel's block shapes: 2 x 3, 3 x 2, 2 x 2 waves, ragged last steps
+                 (40001, 192, 384), (33333, 384, 192), (20011, 384, 384), (9999, 384, 768), (20000, 768, 384), (12345, 128, 256),
+                 # cin % 16 == 8: _LinearFn's forward, rocBLAS input gradient
+                 (3001, 24, 48), (20011, 40, 96)]
+
+
+# rows = bf16: SEG3D_TRAIN_STORAGE=bf16, the weight gradient multiplies a bf16 copy of x (seg3d_linear_wgrad_partials_xbf16)
+@pytest.mark.parametrize("m,cin,cout,rows", [pytest.param(*s, r, id="-".join(map(str, s)) + ("-bf16rows" if r == "bf16" else ""))
+                                             for s in _WGRAD_SHAPES for r in ("fp32", "bf16")])
+def test_linear_wgrad_matches_autograd(m, cin, cout, rows, monkeypatch):
     from openseg3d_amd import ops
     dev = torch.device("cuda:0")
     torch.manual_seed(m + cin)
@@ -21,15 +26,26 @@ def test_linear_wgrad_matches_autograd(m, cin, cout):
     xr, wr, br = x.double().requires_grad_(), w.double().requires_grad_(), b.double().requires_grad_()
     torch.nn.functional.linear(xr, wr, br).backward(g.double())
 
-    xg, wg, bg = x.to(dev).requires_grad_(), w.to(dev).requires_grad_(), b.to(dev).requires_grad_()
-    y = ops.linear(xg, wg, bg)
-    assert y.grad_fn is not None and "LinearFn" in type(y.grad_fn).__name__
-    y.backward(g.to(dev))
+    def run(mode):
+        monkeypatch.setattr(ops, "TRAIN_STORAGE", mode)
+        xg, wg, bg = x.to(dev).requires_grad_(), w.to(dev).requires_grad_(), b.to(dev).requires_grad_()
+        y = ops.linear(xg, wg, bg)
+        assert y.grad_fn is not None and "LinearFn" in type(y.grad_fn).__name__
+        y.backward(g.to(dev))
+        return y.detach(), xg.grad, wg.grad, bg.grad
+
+    y, dx, dw, db = run(rows)
+    ref_w = wr.grad
+    if rows == "bf16":
+        # nothing but the weight gradient reads the copy: the forward, dx and db equal the fp32-rows run bit for bit
+        y32, dx32, _, db32 = run("fp32")
+        assert torch.equal(y, y32) and torch.equal(dx, dx32) and torch.equal(db, db32)
+        ref_w = g.double().t() @ x.to(torch.bfloat16).double()  # the operands the kernel is given
     # split-bf16 products: ~2^-16 relative per term, sums of m terms of O(1) values
-    scale = max(1.0, float(wr.grad.abs().max()))
-    assert float((wg.grad.cpu().double() - wr.grad).abs().max()) < 1e-4 * scale
-    assert float((xg.grad.cpu().double() - xr.grad).abs().max()) < 1e-4
-    assert float((bg.grad.cpu().double() - br.grad).abs().max()) < 1e-3 * max(1.0, float(br.grad.abs().max()))
+    scale = max(1.0, float(ref_w.abs().max()))
+    assert float((dw.cpu().double() - ref_w).abs().max()) < 1e-4 * scale
+    assert float((dx.cpu().double() - xr.grad).abs().max()) < 1e-4
+    assert float((db.cpu().double() - br.grad).abs().max()) < 1e-3 * max(1.0, float(br.grad.abs().max()))
 
 
 def test_linear_wgrad_is_reproducible_and_handles_tiny_inputs():

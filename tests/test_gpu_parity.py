@@ -157,10 +157,14 @@ def test_rulebook_dense_scene_and_edges(dev):
 
 
 # ------------------------------------------------------------------------------------------ a9-a11 conv math
-@pytest.mark.parametrize("precision,tol", [("fp32", 2e-5), ("bf16x3", 1e-4)])
+@pytest.mark.parametrize("precision,tol,rows", [pytest.param("fp32", 2e-5, "fp32", id="fp32-2e-05"),
+                                                pytest.param("bf16x3", 1e-4, "fp32", id="bf16x3-0.0001"),
+                                                pytest.param("bf16x3", 1e-4, "bf16", id="bf16x3-0.0001-bf16rows")])
 @pytest.mark.parametrize("cin,cout", [(64, 48), (48, 32), (96, 48), (192, 96), (768, 384)])
-def test_sparse_conv_forward_and_backward(dev, golden_dir, monkeypatch, cin, cout, precision, tol):
-    """fp32 = exact-fp32 MFMA; bf16x3 = split-bf16 products (~2^-16 relative per product)."""
+def test_sparse_conv_forward_and_backward(dev, golden_dir, monkeypatch, cin, cout, precision, tol, rows):
+    """fp32 = exact-fp32 MFMA; bf16x3 = split-bf16 products (~2^-16 relative per product).  rows = bf16: the training
+    forward saves a bf16 copy of x for the weight gradient (SEG3D_TRAIN_STORAGE=bf16): y, dx and db are bit-identical to the
+    fp32-rows run and dW is checked against the float64 gradient of bf16(x)."""
     from oracle import sparse_conv as sc
     from openseg3d_amd import ops, spconv
     monkeypatch.setattr(ops, "CONV_PRECISION", precision)
@@ -175,7 +179,7 @@ def test_sparse_conv_forward_and_backward(dev, golden_dir, monkeypatch, cin, cou
     w = torch.randn(cout, 3, 3, 3, cin, dtype=torch.float64) / (27 * cin) ** 0.5
     b = torch.randn(cout, dtype=torch.float64)
 
-    def run_ref(kind):
+    def run_ref(kind, x=x):
         xr, wr, br = x.clone().requires_grad_(), w.clone().requires_grad_(), b.clone().requires_grad_()
         if kind == "subm":
             y = sc.subm_conv(xr, ref, wr, br)
@@ -185,8 +189,8 @@ def test_sparse_conv_forward_and_backward(dev, golden_dir, monkeypatch, cin, cou
         y.backward(g)
         return y.detach(), g, xr.grad, wr.grad, br.grad
 
-    for kind, cls in (("subm", spconv.SubMConv3d), ("down", spconv.SparseConv3d)):
-        y_ref, g, dx_ref, dw_ref, db_ref = run_ref(kind)
+    def run(kind, cls, g, mode):
+        monkeypatch.setattr(ops, "TRAIN_STORAGE", mode)
         kw = dict(padding=1) if kind == "subm" else dict(stride=2, padding=1, indice_key="k")
         conv = cls(cin, cout, 3, bias=True, **kw).to(dev)
         with torch.no_grad():
@@ -194,13 +198,22 @@ def test_sparse_conv_forward_and_backward(dev, golden_dir, monkeypatch, cin, cou
             conv.bias.copy_(b.float())
         xt = spconv.SparseConvTensor(x.float().to(dev).requires_grad_(), torch.from_numpy(coords).to(dev), shape, bs)
         out = conv(xt)
-        # vs fp64 reference; values are O(1)
-        assert float((out.features.detach().cpu().double() - y_ref).abs().max()) < tol
         out.features.backward(g.float().to(dev))
-        assert float((xt.features.grad.cpu().double() - dx_ref).abs().max()) < tol
-        assert float((conv.bias.grad.cpu().double() - db_ref).abs().max()) < 1e-3 * max(1.0, float(db_ref.abs().max()))
+        return out.features.detach(), xt.features.grad, conv.weight.grad, conv.bias.grad
+
+    for kind, cls in (("subm", spconv.SubMConv3d), ("down", spconv.SparseConv3d)):
+        y_ref, g, dx_ref, dw_ref, db_ref = run_ref(kind)
+        y, dx, dw, db = run(kind, cls, g, rows)
+        # vs fp64 reference; values are O(1)
+        assert float((y.cpu().double() - y_ref).abs().max()) < tol
+        assert float((dx.cpu().double() - dx_ref).abs().max()) < tol
+        if rows == "bf16":
+            y32, dx32, _, db32 = run(kind, cls, g, "fp32")
+            assert torch.equal(y, y32) and torch.equal(dx, dx32) and torch.equal(db, db32), kind
+            dw_ref = run_ref(kind, x.float().to(torch.bfloat16).double())[3]  # the operand the weight gradient is given
+        assert float((db.cpu().double() - db_ref).abs().max()) < 1e-3 * max(1.0, float(db_ref.abs().max()))
         scale = max(1.0, float(dw_ref.abs().max()))
-        assert float((conv.weight.grad.cpu().double() - dw_ref).abs().max()) < 1e-4 * scale
+        assert float((dw.cpu().double() - dw_ref).abs().max()) < 1e-4 * scale
 
 
 @pytest.mark.parametrize("precision,tol", [("fp32", 2e-5), ("bf16x3", 1e-4)])
