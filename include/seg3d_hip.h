@@ -423,13 +423,23 @@ int seg3d_pos_embed(const int32_t* in_win, int64_t m, const int32_t* win_xyz /*h
  * Backward takes the forward's out and lse, returns gradients w.r.t. the raw q, k, v (through the
  * normalisation) and stores the tau gradient in dtau[0] (per-wave partials in the workspace, summed in a
  * fixed order: the whole backward is free of atomics and identical from run to run).
- * Head geometries: dh 6 / 12 with a head count that is a multiple of 4 (dh 6: <= 8 heads), dh 24 / 48 with up to 16 heads
+ * Head geometries: dh 6 with 4 / 8 / 16 heads, dh 12 with 4 / 8 / 12 / 16 heads, dh 24 / 48 with 1 .. 16 heads
  * (the reference builds 8 heads of 6 / 12 / 24 / 48 channels, pointtransformer.py:143-155); seg3d_window_attn_supported
  * returns 1 for those, everything else is refused with SEG3D_EINVAL.  win_tile0 is accepted and ignored (it served
  * kernels removed in ABI 30); the forward needs no workspace, seg3d_window_attn_workspace_bytes sizes the backward's.
  */
 int seg3d_window_attn_supported(int32_t heads, int32_t dh);
 size_t seg3d_window_attn_workspace_bytes(int64_t m, int32_t n_tiles, int32_t heads, int32_t dh);
+/* Host only, no launch: the schedule seg3d_window_attn_fwd (called with an lse) and _bwd take for a window index with
+ * n_tiles 32-token tiles and n_chunks 128-token chunks (counts[2..3] of seg3d_window_partition), computed by the functions
+ * the launchers themselves call.  out[0] forward kernel: 0 fused persistent, 1 vector-ALU (one workgroup per tile);
+ * out[1] forward grid cap = CUs x resident workgroups per CU (0 for the vector-ALU kernel, which has none; with zero items
+ * the cap is still reported); out[2] forward grid; out[3] the most work units -- (item, head group) -- any forward workgroup
+ * walks (1 = the persistent loop is not iterated); out[4] items per XCD block of the forward's item order (the fused backward
+ * deals its blocks the same way; 1 for the vector-ALU kernel); out[5] workgroups of each backward pass, padding included.
+ * SEG3D_EINVAL for a null out, negative counts, n_chunks > n_tiles, dropout_p outside [0, 1) or a head geometry
+ * seg3d_window_attn_supported refuses. */
+int seg3d_window_attn_schedule(int32_t n_tiles, int32_t n_chunks, int32_t heads, int32_t dh, float dropout_p, int32_t* out);
 int seg3d_window_attn_fwd(const float* q, const float* k, const float* v, int32_t ldq, int32_t ldk,
                           int32_t ldv, const int32_t* tok, const int32_t* win_start,
                           const int32_t* win_count, const int32_t* win_tile0,

@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 41
+ABI_VERSION = 42
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -85,6 +85,7 @@ SIGNATURES = {
     "seg3d_pos_embed": (ctypes.c_int, [_p, _i64, _p, _p, _i32, _p, _p]),
     "seg3d_window_attn_supported": (ctypes.c_int, [_i32, _i32]),
     "seg3d_window_attn_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "seg3d_window_attn_schedule": (ctypes.c_int, [_i32, _i32, _i32, _i32, _f, _p]),
     "seg3d_window_attn_fwd": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32,
                                              _i64, _i32, _i32, _i32, _p, _f, _f, _u64, _p, _p, _p, _sz, _p]),
     "seg3d_window_attn_bwd": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p,

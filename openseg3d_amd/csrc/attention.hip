@@ -20,6 +20,9 @@ int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ld
                           const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles,
                           const int32_t* chunk_item, int n_chunks, int heads, int dh, const float* tau, float tau_min,
                           float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st);
+int attn_fused_fwd_schedule(int n_tiles, int n_chunks, int heads, int dh, bool dropout, int* cap, int* grid, int* walked,
+                            int* xb);
+size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh);  // attention_fused_bwd.hip
 size_t attn_fused_bwd_workspace_bytes(int64_t m, int n_tiles, int n_chunks, int heads, int dh);  // attention_fused_bwd.hip
 bool attn_fused_bwd_supported(int heads, int dh);
 int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
@@ -29,6 +32,7 @@ int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ld
                           float* dv, int lddq, int lddk, int lddv, float* dtau, void* workspace, const DropoutParams& drop,
                           hipStream_t st);
 bool attn_small_supported(int heads, int dh);  // attention_small.hip
+size_t attn_small_blocks(int n_tiles);
 int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
                           const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads,
                           int dh, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
@@ -47,6 +51,16 @@ int bwd_path(int heads, int dh) {
     if (attn_fused_bwd_supported(heads, dh)) return 0;
     if (attn_small_supported(heads, dh)) return 1;
     return -1;
+}
+
+// dh 6 (stage 1: windows of ~15 voxels) WITH dropout: exact fp32 on the vector ALUs, like its backward -- one hash per key
+// pair and thread instead of the MFMA kernel's per-fragment mask: 101 -> 86 / 96 -> 73 us per layer (shift 0 / 1).  Without
+// dropout the two forms tie (84 / 67 against 72 / 66 us) and the fused kernel stays.  SEG3D_ATTN_SMALL_FWD=0 | 1 | 2 (A/B):
+// never / with dropout (default) / always.  (The vector-ALU kernel always writes the LSE: a caller that passes none stays
+// on the fused one.)
+bool small_fwd_runs(int heads, int dh, float dropout_p, bool has_lse) {
+    static const int small_fwd = getenv("SEG3D_ATTN_SMALL_FWD") ? atoi(getenv("SEG3D_ATTN_SMALL_FWD")) : 1;
+    return (small_fwd == 2 || (small_fwd == 1 && dropout_p > 0.f)) && attn_small_supported(heads, dh) && has_lse;
 }
 
 bool rows_misaligned(const void* a, const void* b, const void* c, int lda, int ldb, int ldc) {
@@ -69,10 +83,29 @@ size_t seg3d_window_attn_workspace_bytes(int64_t m, int32_t n_tiles, int32_t hea
     size_t bwd = 0;
     switch (bwd_path(heads, dh)) {
         case 0: bwd = attn_fused_bwd_workspace_bytes(m, n_tiles, n_tiles, heads, dh); break;  // chunks <= tiles
-        case 1: bwd = (size_t)n_tiles * sizeof(float); break;
+        case 1: bwd = attn_small_blocks(n_tiles) * sizeof(float); break;
         default: return 0;
     }
     return bwd + 256;
+}
+
+// Host only (no launch): the kernels and grids seg3d_window_attn_fwd (given an lse) / _bwd take for these counts, from the
+// same functions the launchers call.
+int seg3d_window_attn_schedule(int32_t n_tiles, int32_t n_chunks, int32_t heads, int32_t dh, float dropout_p, int32_t* out) {
+    if (!out || n_tiles < 0 || n_chunks < 0 || n_chunks > n_tiles || !(dropout_p >= 0.f && dropout_p < 1.f) ||
+        !seg3d_window_attn_supported(heads, dh))
+        return SEG3D_EINVAL;
+    if (small_fwd_runs(heads, dh, dropout_p, true)) {  // one workgroup per tile: no cap, no walk, no XCD blocks
+        const int blocks = (int)attn_small_blocks(n_tiles);
+        out[0] = 1, out[1] = 0, out[2] = blocks, out[3] = blocks > 0 ? 1 : 0, out[4] = 1;
+    } else {
+        int cap = 0, grid = 0, walked = 0, xb = 0;
+        const int rc = attn_fused_fwd_schedule(n_tiles, n_chunks, heads, dh, dropout_p > 0.f, &cap, &grid, &walked, &xb);
+        if (rc != SEG3D_OK) return rc;
+        out[0] = 0, out[1] = cap, out[2] = grid, out[3] = walked, out[4] = xb;
+    }
+    out[5] = (int32_t)(bwd_path(heads, dh) == 0 ? attn_fused_bwd_blocks(n_tiles, n_chunks, heads, dh) : attn_small_blocks(n_tiles));
+    return SEG3D_OK;
 }
 
 int seg3d_window_attn_fwd(const float* q, const float* k, const float* v, int32_t ldq, int32_t ldk, int32_t ldv,
@@ -90,12 +123,7 @@ int seg3d_window_attn_fwd(const float* q, const float* k, const float* v, int32_
         return SEG3D_EINVAL;
     if (!attn_fused_supported(heads, dh)) return SEG3D_EINVAL;
     if (rows_misaligned(q, k, v, ldq, ldk, ldv)) return SEG3D_EINVAL;  // rows are gathered in 16-B pieces
-    // dh 6 (stage 1: windows of ~15 voxels) WITH dropout: exact fp32 on the vector ALUs, like its backward -- one hash per key
-    // pair and thread instead of the MFMA kernel's per-fragment mask: 101 -> 86 / 96 -> 73 us per layer (shift 0 / 1).  Without
-    // dropout the two forms tie (84 / 67 against 72 / 66 us) and the fused kernel stays.  SEG3D_ATTN_SMALL_FWD=0 | 1 | 2 (A/B):
-    // never / with dropout (default) / always.
-    static const int small_fwd = getenv("SEG3D_ATTN_SMALL_FWD") ? atoi(getenv("SEG3D_ATTN_SMALL_FWD")) : 1;
-    if ((small_fwd == 2 || (small_fwd == 1 && dropout_p > 0.f)) && attn_small_supported(heads, dh) && lse)
+    if (small_fwd_runs(heads, dh, dropout_p, lse != nullptr))
         return attn_small_fwd_launch(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, tile_item, n_tiles, heads, dh, tau, tau_min,
                                      out, lse, make_dropout(dropout_p, dropout_seed), as_stream(stream));
     return attn_fused_fwd_launch(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, tile_item, n_tiles, qg_item, n_qgroups,
@@ -130,7 +158,7 @@ int seg3d_window_attn_bwd(const float* q, const float* k, const float* v, int32_
                                      qg_item, n_qgroups, m, heads, dh, tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau,
                                      workspace, drop, as_stream(stream));
     }
-    if (workspace_bytes < (size_t)n_tiles * sizeof(float)) return SEG3D_EWORKSPACE;
+    if (workspace_bytes < attn_small_blocks(n_tiles) * sizeof(float)) return SEG3D_EWORKSPACE;
     return attn_small_bwd_launch(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, tile_item, n_tiles, heads,
                                  dh, tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, workspace, drop, as_stream(stream));
 }

@@ -121,10 +121,8 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
     // share one; placement is a speed matter only), so group x takes the items = x (mod xcd_groups) and walks them with
     // its own workgroups side by side: at any moment one XCD works on a handful of windows, all heads of each.
     const int XG = xcd_groups;                  // 1 = flat order
-    const int gx = (int)blockIdx.x % XG, gs = (int)blockIdx.x / XG;
-    const int S = ((int)gridDim.x - gx + XG - 1) / XG;       // workgroups of my group
-    const int units_x = xcd_block_count(n_items, gx, XG, xcd_block) * hgn;  // units of my group: u = s + j * S
-    const int J = units_x > gs ? (units_x - gs + S - 1) / S : 0;
+    const FwdWalk walk = fwd_walk(n_items, hgn, (int)gridDim.x, (int)blockIdx.x, XG, xcd_block);  // attn_fused.hpp
+    const int gx = walk.gx, gs = walk.gs, S = walk.S, J = walk.J;  // units of this workgroup: u = gs + j * S, j < J
     auto unit_of = [&](int j, int* item, int* hg) {
         const int u = gs + j * S;
         *item = xcd_block_item(u / hgn, gx, XG, xcd_block);  // blocks of consecutive items (one window's tiles) per XCD
@@ -573,15 +571,17 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
 #endif
 }
 
+// The forward's schedule for one call: one round of resident workgroups (persistent): CUs x workgroups per CU, or fewer
+// when there is less work.  launch<DH>() and seg3d_window_attn_schedule (attn_fused_fwd_schedule below) both take it from here.
+struct FwdSchedule {
+    int n_items, hgn;  // items of the list this head width walks (tiles / chunks), head groups per item
+    int cap, grid;     // CUs x resident workgroups per CU; workgroups launched
+    int xg, xb;        // XCD groups, items per XCD block
+};
+
 template <int DH>
-int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-           const int32_t* win_start, const int32_t* win_count, const int4* tile_item, int n_tiles, const int4* chunk_item,
-           int n_chunks, int heads, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-           hipStream_t st) {
+FwdSchedule fwd_schedule(int n_tiles, int n_chunks, int heads, bool dropout) {
     using C = Cfg<DH>;
-    const int4* items = C::kNarrow ? tile_item : chunk_item;
-    const int n_items = C::kNarrow ? n_tiles : n_chunks;
-    // one round of resident workgroups (persistent): CUs x workgroups per CU, or fewer when there is less work
     static const int n_cu = [] {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) {
@@ -591,14 +591,31 @@ int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int
         return cus;
     }();
     static const int per_cu_env = getenv("SEG3D_ATTN_WGS_PER_CU") ? atoi(getenv("SEG3D_ATTN_WGS_PER_CU")) : 0;  // A/B
-    const int per_cu = per_cu_env > 0 ? per_cu_env : FwdGeo<DH>::waves(drop.threshold != 0);
-    const long long total = (long long)n_items * (heads / C::HG);
     static const int xcd_env = getenv("SEG3D_ATTN_XCD") ? atoi(getenv("SEG3D_ATTN_XCD")) : 8;  // A/B: 1 = flat order
-    const int xg = xcd_env > 0 ? xcd_env : 8;
-    const int xb = xg == 1 ? 1 : xcd_block_items(C::kNarrow, n_items);
-    long long wgs = total < (long long)n_cu * per_cu ? total : (long long)n_cu * per_cu;
-    wgs = (wgs + xg - 1) / xg * xg;  // whole groups (a workgroup without units returns at once)
-    const dim3 grid((unsigned)wgs);
+    FwdSchedule s;
+    s.n_items = C::kNarrow ? n_tiles : n_chunks;
+    s.hgn = heads / C::HG;
+    const int per_cu = per_cu_env > 0 ? per_cu_env : FwdGeo<DH>::waves(dropout);
+    s.cap = n_cu * per_cu;
+    const long long total = (long long)s.n_items * s.hgn;
+    s.xg = xcd_env > 0 ? xcd_env : 8;
+    s.xb = s.xg == 1 ? 1 : xcd_block_items(C::kNarrow, s.n_items);
+    long long wgs = total < (long long)s.cap ? total : (long long)s.cap;
+    wgs = (wgs + s.xg - 1) / s.xg * s.xg;  // whole groups (a workgroup without units returns at once)
+    s.grid = (int)wgs;
+    return s;
+}
+
+template <int DH>
+int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
+           const int32_t* win_start, const int32_t* win_count, const int4* tile_item, int n_tiles, const int4* chunk_item,
+           int n_chunks, int heads, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
+           hipStream_t st) {
+    using C = Cfg<DH>;
+    const int4* items = C::kNarrow ? tile_item : chunk_item;
+    const FwdSchedule s = fwd_schedule<DH>(n_tiles, n_chunks, heads, drop.threshold != 0);
+    const int n_items = s.n_items, xg = s.xg, xb = s.xb;
+    const dim3 grid((unsigned)s.grid);
     if (drop.threshold)
         hipLaunchKernelGGL((attn_fused_fwd<DH, true>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, tok, win_start, win_count,
                            items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb);
@@ -607,6 +624,17 @@ int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int
                            items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
+}
+
+template <int DH>
+void schedule_out(int n_tiles, int n_chunks, int heads, bool dropout, int* cap, int* grid, int* walked, int* xb) {
+    const FwdSchedule s = fwd_schedule<DH>(n_tiles, n_chunks, heads, dropout);
+    int most = 0;
+    for (int bid = 0; bid < s.grid && bid < s.xg; ++bid) {  // the first workgroup of a group walks the most of that group
+        const int j = fwd_walk(s.n_items, s.hgn, s.grid, bid, s.xg, s.xb).J;
+        most = j > most ? j : most;
+    }
+    *cap = s.cap, *grid = s.grid, *walked = most, *xb = s.xb;
 }
 
 }  // namespace
@@ -629,6 +657,19 @@ int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ld
         case 12: return launch<12>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st);
         case 24: return launch<24>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st);
         case 48: return launch<48>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st);
+        default: return SEG3D_EINVAL;
+    }
+}
+
+// host only: what launch<dh>() would launch for these counts -- the grid cap (CUs x resident workgroups per CU), the grid, the
+// most units one workgroup walks and the XCD block size
+int attn_fused_fwd_schedule(int n_tiles, int n_chunks, int heads, int dh, bool dropout, int* cap, int* grid, int* walked,
+                            int* xb) {
+    switch (dh) {
+        case 6: schedule_out<6>(n_tiles, n_chunks, heads, dropout, cap, grid, walked, xb); return SEG3D_OK;
+        case 12: schedule_out<12>(n_tiles, n_chunks, heads, dropout, cap, grid, walked, xb); return SEG3D_OK;
+        case 24: schedule_out<24>(n_tiles, n_chunks, heads, dropout, cap, grid, walked, xb); return SEG3D_OK;
+        case 48: schedule_out<48>(n_tiles, n_chunks, heads, dropout, cap, grid, walked, xb); return SEG3D_OK;
         default: return SEG3D_EINVAL;
     }
 }

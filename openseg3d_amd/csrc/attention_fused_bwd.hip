@@ -38,6 +38,8 @@ extern "C" int seg3d_debug_attn_bwd_stamps(void* buf) {
 #define BSTAMP(var) do {} while (0)
 #endif
 
+size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh);  // below: blocks of each pass
+
 namespace {
 
 using namespace attn;
@@ -189,6 +191,7 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
     }
     const int4 item = items[item_i];  // {window, tile / chunk, first token slot, tokens}: one round trip less in front of the gathers
     const int n = item.w, start = item.z;
+    const float log2n = __builtin_amdgcn_logf((float)n);  // (v_log_f32 = log2) for the tau gradient's row constant
     const int n_t = (n + 31) >> 5;  // 32-token tiles of the window (streamed and stationary alike)
     const int h0 = (gu % hgn) * HG;
     const int c_all = heads * DH;
@@ -598,7 +601,12 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
                     else if constexpr (DROP) ds2 = __builtin_elementwise_fma(pk2, dp2, -(p2 * d2));
                     else ds2 = p2 * (dp2 - d2);
                     dsv[u * 2 + r2] = ds2;
-                    if (MODE == 0) tau2[j] = __builtin_elementwise_fma(ds2, s2, tau2[j]);
+                    // dtau += <dS, S - c>: sum_j dS = 0 along a query's row (under dropout too: delta carries the mask), so any
+                    // row constant c may be taken off S, and in floating point it should be: the row sum cancels only to
+                    // rounding, and what is left of it comes back times |S - c|.  c = LSE - log2 n, the log of the row's MEAN
+                    // exp, lies between the row's mean and its largest score, so the terms that carry weight stay O(log2 n)
+                    // at every tau, where S itself reaches log2e / tau = 72 at tau 0.02
+                    if (MODE == 0) tau2[j] = __builtin_elementwise_fma(ds2, e2 + (f32x2){log2n, log2n}, tau2[j]);
                     else pv[u * 2 + r2] = pk2;          // dV = (D P)^T dO
                 }
             }
@@ -783,12 +791,6 @@ __global__ __launch_bounds__(1024) void tau_reduce_fused(const float* __restrict
     }
 }
 
-// blocks of a pass: whole groups of 8 items x head groups (the kernel's block -> (item, head group) map)
-static size_t bwd_blocks(int n_items, int hgn, int xb) {
-    const size_t per = (size_t)8 * xb;
-    return (n_items + per - 1) / per * per * hgn;
-}
-
 template <int DH>
 int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out, const float* dout,
            const float* lse, const int32_t* tok, const int32_t* win_start, const int32_t* win_count, const int4* tile_item,
@@ -799,7 +801,7 @@ int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int
     const int4* items = C::kNarrow ? tile_item : chunk_item;
     const int n_items = C::kNarrow ? n_tiles : n_chunks;
     const int xb = xcd_block_items(C::kNarrow, n_items);
-    const dim3 grid((unsigned)(bwd_blocks(n_items, heads / C::HG, xb)));
+    const dim3 grid((unsigned)attn_fused_bwd_blocks(n_tiles, n_chunks, heads, DH));
     hipLaunchKernelGGL((attn_fused_bwd<DH, 0>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start,
                        win_count, items, n_items, heads, tau, tau_min, dq, lddq, dk, lddk, dv, lddv, tau_part, delta_buf, drop, xb);
     SEG3D_CHECK_LAUNCH();
@@ -821,9 +823,15 @@ bool attn_fused_bwd_supported(int heads, int dh) {
     return (dh == 12 && heads % 4 == 0) || dh == 24 || dh == 48;
 }
 
+// blocks of each of the two passes (attn_fused.hpp: bwd_blocks): 32-token tiles x groups of 4 heads for dh 6 / 12,
+// 128-token chunks x heads for dh 24 / 48.  The launch, the workspace size and seg3d_window_attn_schedule read it here.
+size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh) {
+    return dh <= 12 ? bwd_blocks(n_tiles, heads / 4, xcd_block_items(true, n_tiles))
+                    : bwd_blocks(n_chunks, heads, xcd_block_items(false, n_chunks));
+}
+
 static size_t tau_part_bytes(int n_tiles, int n_chunks, int heads, int dh) {
-    const size_t blocks = (dh <= 12) ? bwd_blocks(n_tiles, heads / 4, xcd_block_items(true, n_tiles)) : bwd_blocks(n_chunks, heads, xcd_block_items(false, n_chunks));
-    return align_up(blocks * 4 * sizeof(float), 256);
+    return align_up(attn_fused_bwd_blocks(n_tiles, n_chunks, heads, dh) * 4 * sizeof(float), 256);
 }
 
 // one dtau partial per wave of pass Q + delta = <dO, O> per (token, head), handed from pass Q to pass KV

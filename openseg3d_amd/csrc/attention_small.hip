@@ -15,6 +15,9 @@
 #include "attn_common.hpp"
 #include "attn_dropout.hpp"
 
+size_t attn_small_blocks(int n_tiles);  // below: workgroups of every launch in this file
+bool attn_small_supported(int heads, int dh);
+
 namespace {
 
 using namespace attn;
@@ -112,14 +115,20 @@ __device__ __forceinline__ void through_normalise(const Vec<DH>& x_raw, Vec<DH>*
 }
 
 constexpr int kTile = 32;
+// Threads of a workgroup = 32 tokens x heads.  The kernels are built for two workgroup sizes: 256 (up to 8 heads -- the
+// reference's geometry; its code is what it was with that one size) and 512 (16 heads), same registers per thread: 58 / 72 / 115
+// VGPRs for forward / pass Q / pass KV and no scratch in either build (NumVgprs / ScratchSize of the compiler's resource summary
+// of the gfx950 device code, hipcc -S --cuda-device-only with the build's flags); a 512-thread workgroup is 2 waves per SIMD,
+// so even pass KV's 115 registers leave room for two workgroups per CU.
+constexpr int kMaxHeads = 16;
 
 // ------------------------------------------------------------------ forward: out = softmax(q^.k^ / tau) (. dropout) v, LSE
 // Thread (query i, head h) of a (window, 32-token tile) item walks the window's keys 32 at a time through LDS.  Cosine scores
 // are bounded by log2e / tau: that bound is the fixed softmax maximum while exp2(-2 bound) stays a normal float (tau > ~0.036),
 // otherwise the running-maximum form -- a block-uniform choice on the device scalar tau.  The row sum is taken BEFORE the
 // dropout factor (cosine_msa.py:172-176: softmax, then F.dropout, then attn @ v).
-template <int DH>
-__global__ __launch_bounds__(256, 8) void attn_small_fwd(const float* __restrict__ q, const float* __restrict__ k,
+template <int DH, int THREADS>
+__global__ __launch_bounds__(THREADS, 8) void attn_small_fwd(const float* __restrict__ q, const float* __restrict__ k,
                                                       const float* __restrict__ v, int ldq, int ldk, int ldv,
                                                       const int32_t* __restrict__ tok, const int32_t* __restrict__ win_start,
                                                       const int32_t* __restrict__ win_count, const int4* __restrict__ tile_item,
@@ -201,8 +210,8 @@ __global__ __launch_bounds__(256, 8) void attn_small_fwd(const float* __restrict
 }
 
 // ------------------------------------------------------------------ backward, pass Q: dq, dtau
-template <int DH>
-__global__ __launch_bounds__(256, 2) void attn_small_bwd_q(const float* __restrict__ q, const float* __restrict__ k,
+template <int DH, int THREADS>
+__global__ __launch_bounds__(THREADS, 2) void attn_small_bwd_q(const float* __restrict__ q, const float* __restrict__ k,
                                                         const float* __restrict__ v, int ldq, int ldk, int ldv,
                                                         const float* __restrict__ out, const float* __restrict__ dout,
                                                         const float* __restrict__ lse, const int32_t* __restrict__ tok,
@@ -214,7 +223,7 @@ __global__ __launch_bounds__(256, 2) void attn_small_bwd_q(const float* __restri
     const int c = heads * DH;
     float* kbuf = smem;
     float* vbuf = smem + kTile * c;
-    __shared__ float tau_red[8];
+    __shared__ float tau_red[kMaxHeads / 2];  // one per wave
     const int i = threadIdx.x & 31, h = threadIdx.x >> 5;
     const int4 item = tile_item[blockIdx.x];
     const int n = item.w, start = item.z;
@@ -233,6 +242,11 @@ __global__ __launch_bounds__(256, 2) void attn_small_bwd_q(const float* __restri
         l2 = lse[(int64_t)qtok * heads + h] * kLog2e;
     }
     float tau_acc = 0.f;
+    // dtau = sum ds * (s - c): sum_j ds = 0 along a row, so any row constant c may be taken off s, and in floating point it should
+    // be -- the row sum cancels only to rounding (the LSE may come from the fused forward's split-bf16 scores, these are exact
+    // fp32), and what is left of it comes back times |s - c|.  c = LSE - log2 n, the log of the row's MEAN exp, lies between the
+    // row's mean and its largest score: the terms that carry weight stay O(log2 n) at every tau (s reaches 72 at tau 0.02)
+    const float tau_shift = l2 - __builtin_amdgcn_logf((float)n);
     // dropout: the query's share of the hash (two mixing rounds) once per thread; its parity picks the byte pair of every block
     const uint32_t row_state = drop.threshold ? dropout_row_state(dropout_head_state(drop, item.x, h), qi) : 0u;
     const uint32_t drop_shift = dropout_lane_shift_query(qi & 1);
@@ -274,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void attn_small_bwd_q(const float* __restri
                     float dpv = dot(go, vv);
                     if (drop.threshold) dpv = dropout_dropped_byte(drop, adj, u) ? 0.f : dpv * drop.inv_keep;
                     const float ds = p * (dpv - delta);
-                    tau_acc = fmaf(ds, s, tau_acc);
+                    tau_acc = fmaf(ds, s - tau_shift, tau_acc);
                     axpy<DH>(ds, kk, &acc);
                 }
             }
@@ -299,8 +313,8 @@ __global__ __launch_bounds__(256, 2) void attn_small_bwd_q(const float* __restri
 }
 
 // ------------------------------------------------------------------ backward, pass KV: dk, dv
-template <int DH>
-__global__ __launch_bounds__(256, 3) void attn_small_bwd_kv(const float* __restrict__ q, const float* __restrict__ k,
+template <int DH, int THREADS>
+__global__ __launch_bounds__(THREADS, 3) void attn_small_bwd_kv(const float* __restrict__ q, const float* __restrict__ k,
                                                          const float* __restrict__ v, int ldq, int ldk, int ldv,
                                                          const float* __restrict__ out, const float* __restrict__ dout,
                                                          const float* __restrict__ lse, const int32_t* __restrict__ tok,
@@ -409,20 +423,20 @@ __global__ __launch_bounds__(1024) void tau_reduce_small(const float* __restrict
     }
 }
 
-template <int DH>
+template <int DH, int THREADS>
 int run_small_bwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
                   const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
                   const int32_t* win_count, const int4* tile_item, int n_tiles, int heads, const float* tau, float tau_min,
                   float* dq, float* dk, float* dv, int lddq, int lddk, int lddv, float* dtau, float* tau_part,
                   const DropoutParams& drop, hipStream_t st) {
     const size_t smem_q = (size_t)2 * kTile * heads * DH * sizeof(float);
-    hipLaunchKernelGGL(attn_small_bwd_q<DH>, dim3((unsigned)n_tiles), dim3(32 * heads), smem_q, st, q, k, v, ldq, ldk, ldv,
+    hipLaunchKernelGGL((attn_small_bwd_q<DH, THREADS>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem_q, st, q, k, v, ldq, ldk, ldv,
                        out, dout, lse, tok, win_start, win_count, tile_item, heads, tau, tau_min, dq, lddq, tau_part, drop);
     SEG3D_CHECK_LAUNCH();
     hipLaunchKernelGGL(tau_reduce_small, dim3(1), dim3(1024), 0, st, tau_part, n_tiles, dtau);
     SEG3D_CHECK_LAUNCH();
     const size_t smem_kv = smem_q + (size_t)kTile * heads * 2 * sizeof(float);
-    hipLaunchKernelGGL(attn_small_bwd_kv<DH>, dim3((unsigned)n_tiles), dim3(32 * heads), smem_kv, st, q, k, v, ldq, ldk, ldv,
+    hipLaunchKernelGGL((attn_small_bwd_kv<DH, THREADS>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem_kv, st, q, k, v, ldq, ldk, ldv,
                        out, dout, lse, tok, win_start, win_count, tile_item, heads, tau, tau_min, dk, lddk, dv, lddv, drop);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
@@ -436,14 +450,24 @@ int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ld
                           hipStream_t st) {
     if (dh != 6) return SEG3D_EINVAL;
     const size_t smem = (size_t)2 * kTile * heads * 6 * sizeof(float);
-    hipLaunchKernelGGL(attn_small_fwd<6>, dim3((unsigned)n_tiles), dim3(32 * heads), smem, st, q, k, v, ldq, ldk, ldv, tok,
-                       win_start, win_count, reinterpret_cast<const int4*>(tile_item), heads, tau, tau_min, out, lse, drop);
+    if (!attn_small_supported(heads, dh)) return SEG3D_EINVAL;
+    if (heads <= 8)
+        hipLaunchKernelGGL((attn_small_fwd<6, 256>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem, st, q, k, v, ldq, ldk, ldv, tok,
+                           win_start, win_count, reinterpret_cast<const int4*>(tile_item), heads, tau, tau_min, out, lse, drop);
+    else
+        hipLaunchKernelGGL((attn_small_fwd<6, 512>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem, st, q, k, v, ldq, ldk, ldv, tok,
+                           win_start, win_count, reinterpret_cast<const int4*>(tile_item), heads, tau, tau_min, out, lse, drop);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }
 
-// used by seg3d_window_attn_fwd / _bwd (attention.hip): dh 6, up to 8 heads
-bool attn_small_supported(int heads, int dh) { return dh == 6 && heads >= 1 && heads <= 8; }
+// one workgroup per (window, 32-token tile) item in the forward and in both backward passes (no persistent loop); also read by
+// seg3d_window_attn_schedule
+size_t attn_small_blocks(int n_tiles) { return n_tiles > 0 ? (size_t)n_tiles : 0; }
+
+// used by seg3d_window_attn_fwd / _bwd (attention.hip): dh 6 with up to 8 heads (one 256-thread workgroup) or with 16 (the
+// 512-thread build; head counts in between stay refused, as they always were)
+bool attn_small_supported(int heads, int dh) { return dh == 6 && heads >= 1 && (heads <= 8 || heads == kMaxHeads); }
 
 int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
                           const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
@@ -453,6 +477,10 @@ int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ld
     if (dh != 6) return SEG3D_EINVAL;
     const int4* ti = reinterpret_cast<const int4*>(tile_item);
     float* tau_part = static_cast<float*>(workspace);  // n_tiles floats
-    return run_small_bwd<6>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, heads, tau,
-                            tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st);
+    if (!attn_small_supported(heads, dh)) return SEG3D_EINVAL;
+    if (heads <= 8)
+        return run_small_bwd<6, 256>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, heads, tau,
+                                     tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st);
+    return run_small_bwd<6, 512>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, heads, tau,
+                                 tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st);
 }

@@ -84,4 +84,27 @@ inline int xcd_block_items(bool narrow, int n_items) {
     return env > 0 ? env : (narrow ? 8 : (n_items >= 512 ? 4 : 1));
 }
 
+// The persistent forward's walk: workgroup `bid` of a grid of `grid` belongs to XCD group gx = bid % xg, is that group's
+// gs-th of S, and takes the units (item slot, head group) u = gs + j * S, j < J, of its group.  The kernel and the host's
+// schedule query (seg3d_window_attn_schedule) both read it from here.
+struct FwdWalk {
+    int gx, gs, S, J;
+};
+__host__ __device__ __forceinline__ FwdWalk fwd_walk(int n_items, int hgn, int grid, int bid, int xg, int xb) {
+    FwdWalk w;
+    w.gx = bid % xg;
+    w.gs = bid / xg;
+    w.S = (grid - w.gx + xg - 1) / xg;                                // workgroups of my group
+    const int units_x = xcd_block_count(n_items, w.gx, xg, xb) * hgn;  // units of my group
+    w.J = units_x > w.gs ? (units_x - w.gs + w.S - 1) / w.S : 0;
+    return w;
+}
+
+// blocks of a backward pass: whole groups of 8 blocks of xb items, times head groups (the kernel's block -> (item, head
+// group) map; the padding blocks leave at once)
+inline size_t bwd_blocks(int n_items, int hgn, int xb) {
+    const size_t per = (size_t)8 * xb;
+    return (n_items + per - 1) / per * per * hgn;
+}
+
 }  // namespace attn_fused

@@ -1691,7 +1691,7 @@ def window_attention_packed(qk, v, tau, tau_min, heads, wi, drop_p=0.0, drop_see
     if v.shape[1] % heads or not _lib.load().seg3d_window_attn_supported(int(heads), v.shape[1] // int(heads)):
         raise _lib.Seg3dError(
             f"window attention: {heads} heads on {v.shape[1]} channels is not a head geometry of this path (head widths "
-            "6 / 12 with a head count that is a multiple of 4, 24 / 48 with up to 16 heads; the reference builds 8 heads "
+            "6 with 4 / 8 / 16 heads, 12 with 4 / 8 / 12 / 16 heads, 24 / 48 with up to 16 heads; the reference builds 8 heads "
             "on 48 / 96 / 192 / 384 channels, pointtransformer.py:143-155)")
     return _WindowAttnPackedFn.apply(qk, v, tau, tau_min, heads, wi, float(drop_p), int(drop_seed))
 

@@ -70,6 +70,26 @@ def test_host_only_entry_points():
         assert _lib.query("seg3d_linear_packed_bytes_x6", cin, cout) == 0
     assert _lib.load().seg3d_linear_fwd_x6(None, 10, None, None, None, None, 0, 128, 256, None, None) == _lib.EINVAL
     assert _lib.load().seg3d_linear_fwd_x6(None, 0, None, None, None, None, 0, 128, 256, None, None) == 0  # nothing to do
+    # the window-attention schedule query (host arithmetic of the launchers, no launch): null output, unsupported head
+    # geometries, more chunks than tiles and a dropout rate outside [0, 1) are refused; an empty index has an empty grid
+    sched = (ctypes.c_int32 * 6)(*([-7] * 6))
+    lib = _lib.load()
+    assert lib.seg3d_window_attn_schedule(59, 23, 8, 12, 0.0, None) == _lib.EINVAL
+    for heads, dh in ((3, 12), (6, 6), (12, 6), (8, 32), (17, 24), (0, 24), (20, 6)):
+        assert lib.seg3d_window_attn_schedule(59, 23, heads, dh, 0.0, sched) == _lib.EINVAL, (heads, dh)
+    assert lib.seg3d_window_attn_schedule(23, 59, 8, 12, 0.0, sched) == _lib.EINVAL
+    assert lib.seg3d_window_attn_schedule(-1, -1, 8, 12, 0.0, sched) == _lib.EINVAL
+    assert lib.seg3d_window_attn_schedule(59, 23, 8, 12, 1.0, sched) == _lib.EINVAL
+    assert list(sched) == [-7] * 6  # a refused call writes nothing
+    assert lib.seg3d_window_attn_schedule(0, 0, 8, 24, 0.0, sched) == 0
+    assert sched[0] == 0 and sched[1] > 0 and list(sched)[2:4] == [0, 0] and sched[5] == 0
+    # 59 tiles x 2 groups of 4 heads: fewer units than any cap, grid = units rounded up to the 8 XCD groups (exact values: the
+    # A/B switches SEG3D_ATTN_XCD, SEG3D_ATTN_XCD_BLOCK and SEG3D_ATTN_WGS_PER_CU must be unset, as in every test run)
+    assert lib.seg3d_window_attn_schedule(59, 23, 8, 12, 0.0, sched) == 0
+    cap = sched[1]
+    assert cap >= 120 and list(sched) == [0, cap, 120, 2, 8, 128]
+    # as many items as the cap, 8 heads each: eight rounds of the full grid
+    assert lib.seg3d_window_attn_schedule(cap, cap, 8, 48, 0.0, sched) == 0 and sched[3] >= 8 and sched[2] == sched[1]
     # both weight-gradient kernels fit the workspace the query reports; the opt-in switch validates its argument
     assert _lib.query("seg3d_linear_wgrad_workspace_bytes", 58453, 192, 192) >= 8 * (192 * 192 + 192) * 4
     assert _lib.load().seg3d_debug_set_wgrad_lds(2) == _lib.EINVAL and _lib.load().seg3d_debug_set_wgrad_lds(-1) == 0

@@ -6,14 +6,9 @@ import numpy as np
 import pytest
 import torch
 
-import refcfg
-
 pytestmark = pytest.mark.gpu
 
-WINDOW_SIZES = [1, 2, 15, 16, 17, 31, 32, 33, 64, 100, 129, 257, 300, 640]
-# windows whose LAST 32-token tile holds 16 / 17 tokens (the backward skips the tile's empty second half) and the 128-token
-# chunk edge with the same remainders
-HALF_TILE_SIZES = [48, 49, 80, 81, 144, 145, 176, 177]
+from attn_ref import HALF_TILE_SIZES, WINDOW_SIZES, reference, windows_of  # noqa: E402,F401  (shared with test_gpu_attention_scale.py)
 
 
 @pytest.fixture(scope="module")
@@ -21,58 +16,17 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _windows_of(dev, sizes):
-    from openseg3d_amd.swformer import SparseWindowPartitionLayer
-    rs = np.random.RandomState(0)
-    rows = []
-    for i, n in enumerate(sizes):
-        cells = rs.permutation(800)[:n]
-        z, y, x = cells // 100, (cells // 10) % 10, cells % 10
-        rows.append(np.stack([np.zeros(n), z + 8, y + 10 * (1 + i % 3), x + 10 * (1 + i)], axis=1))
-    coords = np.concatenate(rows).astype(np.int32)
-    coords = coords[rs.permutation(coords.shape[0])]
-    part = SparseWindowPartitionLayer(refcfg.BATCHING_INFO[0], refcfg.WINDOW_SHAPE, refcfg.GRID_CART.tolist())
-    plan = part.plan(torch.from_numpy(coords).to(dev), 1, 48)
-    wi = plan.index[0]
-    counts = wi.win_count[: wi.n_windows].cpu().numpy()
-    assert sorted(counts.tolist()) == sorted(sizes)
-    return wi, coords.shape[0]
-
-
 @pytest.fixture(scope="module")
 def windows(dev):
     """Voxel coordinates whose shift-0 windows hold exactly WINDOW_SIZES tokens, rows shuffled."""
-    return _windows_of(dev, WINDOW_SIZES)
+    ws = windows_of(dev, WINDOW_SIZES)
+    return ws.wi, ws.m
 
 
 @pytest.fixture(scope="module")
 def half_tile_windows(dev):
-    return _windows_of(dev, HALF_TILE_SIZES)
-
-
-def reference(qk, v, tau, tau_min, heads, wi, keep=None):
-    """fp64, one (window, head) at a time; keep[(w, h)] = optional [n, n] dropout factor (0 or 1 / keep_prob)."""
-    m, c = v.shape
-    dh = c // heads
-    q, k = qk[:, :c], qk[:, c:]
-    tok = wi.tok.cpu().long()
-    starts, counts = wi.win_start[: wi.n_windows].cpu().tolist(), wi.win_count[: wi.n_windows].cpu().tolist()
-    out = torch.zeros(m, c, dtype=torch.float64)
-    scale = 1.0 / torch.clamp(tau.reshape(()), min=tau_min)
-    pieces = []
-    for w, (s, n) in enumerate(zip(starts, counts)):
-        rows = tok[s:s + n]
-        for h in range(heads):
-            sl = slice(h * dh, (h + 1) * dh)
-            qh = torch.nn.functional.normalize(q[rows][:, sl], dim=-1, eps=1e-12)
-            kh = torch.nn.functional.normalize(k[rows][:, sl], dim=-1, eps=1e-12)
-            p = torch.softmax(qh @ kh.t() * scale, dim=-1)
-            if keep is not None:
-                p = p * keep[(w, h)]
-            pieces.append((rows, sl, p @ v[rows][:, sl]))
-    for rows, sl, o in pieces:
-        out[rows, sl] = out[rows, sl] + o  # index_put on disjoint (rows, head) blocks: differentiable
-    return out
+    ws = windows_of(dev, HALF_TILE_SIZES)
+    return ws.wi, ws.m
 
 
 @pytest.mark.parametrize("tau", [1.0, 0.2, 0.02, 0.004])
@@ -221,12 +175,108 @@ def test_unsupported_head_geometry_is_refused_with_a_clear_error(dev, windows):
     from openseg3d_amd import _lib, ops
     lib = _lib.load()
     for heads, dh, ok in ((8, 6, 1), (8, 12, 1), (8, 24, 1), (8, 48, 1), (4, 12, 1), (16, 24, 1), (3, 12, 0), (6, 6, 0),
-                          (8, 32, 0), (12, 6, 0), (17, 24, 0)):
+                          (8, 32, 0), (12, 6, 0), (17, 24, 0), (16, 6, 1), (20, 6, 0), (20, 12, 0), (0, 24, 0)):
         assert lib.seg3d_window_attn_supported(heads, dh) == ok, (heads, dh)
     wi, m = windows
     qk, v = torch.randn(m, 72, device=dev), torch.randn(m, 36, device=dev)
     with pytest.raises(_lib.Seg3dError, match="head geometry"):
         ops.window_attention_packed(qk, v, torch.ones(1, 1, 1, device=dev), 0.01, 3, wi)
+
+
+def _fp64_case(windows, heads, dh, tau, p, seed):
+    """Inputs and the fp64 forward / autograd of one head geometry on a window fixture."""
+    wi, m = windows
+    c = heads * dh
+    gen = torch.Generator().manual_seed(1000 * heads + dh + (7 if p else 0))
+    qk = torch.randn(m, 2 * c, generator=gen, dtype=torch.float64)
+    v = torch.randn(m, c, generator=gen, dtype=torch.float64) * 1.5
+    g = torch.randn(m, c, generator=gen, dtype=torch.float64)
+    tau_t = torch.full((1, 1, 1), tau, dtype=torch.float64)
+    keep = None
+    if p > 0:
+        counts = wi.win_count[: wi.n_windows].cpu().tolist()
+        keep = {(w, h): torch.from_numpy(dropout_factors(p, seed, w, h, n)) for w, n in enumerate(counts) for h in range(heads)}
+    qk_r, v_r, tau_r = qk.clone().requires_grad_(), v.clone().requires_grad_(), tau_t.clone().requires_grad_()
+    ref = reference(qk_r, v_r, tau_r, 0.01, heads, wi, keep)
+    ref.backward(g)
+    return qk, v, g, tau_t, ref.detach(), qk_r.grad, v_r.grad, tau_r.grad
+
+
+def _assert_vs_fp64(out, grads, ref, wants, v, tau, p):
+    """The bars of the 8-head cases above: forward 2e-5 f max|v| (3e-5 max|v| with dropout at tau 0.5), dv / dqk 3e-4 f
+    max(1, max|want|), dtau 2e-3 f max(1, |want|), f = max(1, 0.1 / max(tau, 0.01))."""
+    f = max(1.0, 0.1 / max(tau, 0.01))
+    tol = (3e-5 if p else 2e-5 * f) * float(v.abs().max())
+    assert float((out.detach().cpu().double() - ref).abs().max()) < tol
+    for got, want, name in zip(grads, wants, ("dqk", "dv", "dtau")):
+        scale = max(1.0, float(want.abs().max()))
+        assert float((got.cpu().double() - want).abs().max()) < (2e-3 if name == "dtau" else 3e-4) * f * scale, name
+
+
+# every relative of the reference's geometry seg3d_window_attn_supported accepts: 4 / 12 / 16 narrow heads (dh 6: 4 / 16; 1, 3 and 4 groups of
+# four), 1 .. 16 wide heads (the backward's 8-item groups x heads, odd head counts)
+@pytest.mark.parametrize("heads,dh,tau,p", [(4, 6, 0.2, 0.0), (16, 6, 0.2, 0.0), (4, 12, 0.2, 0.0),
+                                            (12, 12, 0.2, 0.0), (1, 24, 0.2, 0.0), (5, 24, 0.2, 0.0), (16, 24, 0.2, 0.0),
+                                            (1, 48, 0.2, 0.0), (3, 48, 0.2, 0.0), (16, 48, 0.2, 0.0),
+                                            (4, 12, 0.5, 0.1), (16, 24, 0.5, 0.1), (16, 6, 0.5, 0.1)])
+def test_head_geometries_vs_fp64(dev, windows, heads, dh, tau, p):
+    from openseg3d_amd import _lib, ops
+    wi, m = windows
+    assert _lib.load().seg3d_window_attn_supported(heads, dh) == 1
+    seed = 0x0F1E_2D3C_4B5A_6978
+    qk, v, g, tau_t, ref, dqk_w, dv_w, dtau_w = _fp64_case(windows, heads, dh, tau, p, seed)
+    qk_g, v_g = qk.float().to(dev).requires_grad_(), v.float().to(dev).requires_grad_()
+    tau_g = tau_t.float().to(dev).requires_grad_()
+    out = ops.window_attention_packed(qk_g, v_g, tau_g, 0.01, heads, wi, p, seed)
+    out.backward(g.float().to(dev))
+    _assert_vs_fp64(out, (qk_g.grad, v_g.grad, tau_g.grad), ref, (dqk_w, dv_w, dtau_w), v, tau, p)
+
+
+@pytest.mark.parametrize("dh", [12, 48])
+def test_row_strided_entry_vs_fp64_and_packed(dev, windows, dh):
+    """ops.window_attention: q, k, v as the three column blocks of ONE [m, 3C] tensor (row stride 3C, what a fused in-projection
+    would hand over): forward and dq / dk / dv / dtau against fp64, and bit for bit what the packed entry returns for the same
+    values (same kernels, other strides)."""
+    from openseg3d_amd import ops
+    wi, m = windows
+    heads, c, tau = 8, 8 * dh, 0.2
+    qk, v, g, tau_t, ref, dqk_w, dv_w, dtau_w = _fp64_case(windows, heads, dh, tau, 0.0, 0)
+    qkv = torch.cat([qk, v], dim=1).float().to(dev).requires_grad_()
+    assert qkv.stride(0) == 3 * c
+    tau_g = tau_t.float().to(dev).requires_grad_()
+    out = ops.window_attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], tau_g, 0.01, heads, wi)
+    out.backward(g.float().to(dev))
+    dqkv = qkv.grad
+    _assert_vs_fp64(out, (dqkv[:, :2 * c], dqkv[:, 2 * c:], tau_g.grad), ref, (dqk_w, dv_w, dtau_w), v, tau, 0.0)
+    qk_p, v_p = qk.float().to(dev).requires_grad_(), v.float().to(dev).requires_grad_()
+    tau_p = tau_t.float().to(dev).requires_grad_()
+    out_p = ops.window_attention_packed(qk_p, v_p, tau_p, 0.01, heads, wi)
+    out_p.backward(g.float().to(dev))
+    assert torch.equal(out, out_p)
+    assert torch.equal(dqkv[:, :2 * c], qk_p.grad) and torch.equal(dqkv[:, 2 * c:], v_p.grad) and torch.equal(tau_g.grad, tau_p.grad)
+
+
+def test_row_strided_entry_refusals(dev, windows):
+    """The documented refusals of ops.window_attention: anything but float32, and a last dimension that is not contiguous."""
+    from openseg3d_amd import _lib, ops
+    wi, m = windows
+    c = 96
+    tau = torch.ones(1, 1, 1, device=dev)
+    q, k, v = (torch.randn(m, c, device=dev) for _ in range(3))
+    for bad in (torch.float64, torch.float16, torch.bfloat16):
+        for i in range(3):
+            args = [q, k, v]
+            args[i] = args[i].to(bad)
+            with pytest.raises(_lib.Seg3dError, match="float32 with a contiguous last dimension"):
+                ops.window_attention(*args, tau, 0.01, 8, wi)
+    wide = torch.randn(m, 2 * c, device=dev)
+    t = torch.randn(c, m, device=dev).t()  # [m, c] with stride (1, m)
+    for i, view in ((0, wide[:, ::2]), (1, t), (2, wide[:, 1::2])):
+        assert view.shape == (m, c) and view.stride(1) != 1
+        args = [q, k, v]
+        args[i] = view
+        with pytest.raises(_lib.Seg3dError, match="float32 with a contiguous last dimension"):
+            ops.window_attention(*args, tau, 0.01, 8, wi)
 
 
 def test_attention_time_does_not_depend_on_tau(dev):

@@ -170,7 +170,8 @@ def test_fullsize_sparse_conv_linearity_and_adjoints(dev, full, kind, cin, cout,
 
 def test_fullsize_window_attention_properties(dev, full):
     """Stage 1 of the headline scene (108 690 tokens, 6 298 windows, narrow heads) and stage 3 shapes on a coarser level
-    (wide heads): softmax rows sum to one (V = const -> out = const), <out(V), G> = <V, dV(G)>, zero rows for no token."""
+    (wide heads): softmax rows sum to one (V = const -> out = const), every key comes from the query's own window (V = one
+    constant per window -> out = that window's), <out(V), G> = <V, dV(G)>, zero rows for no token."""
     from openseg3d_amd import ops, spconv, swformer
     cfg, ds, pts, b = full
     torch.manual_seed(5)
@@ -190,6 +191,16 @@ def test_fullsize_window_attention_properties(dev, full):
             with torch.no_grad():
                 out = ops.window_attention_packed(qk, torch.full((m, c), 1.5, device=dev), tau, 0.01, 8, wi)
             assert float((out - 1.5).abs().max()) <= 1e-4                  # every softmax row sums to 1
+            # V constant within a window and different from window to window (and from channel to channel), in [1, 2): a key
+            # taken from ANOTHER window moves the row off its own window's value, which one constant for all cannot show
+            # (neighbours in the window list are 2481 / 4096 apart, windows 4096 apart in the list share a value)
+            nw = wi.n_windows
+            win_of = torch.empty(m, dtype=torch.long, device=dev)
+            win_of[wi.tok[:m].long()] = torch.repeat_interleave(torch.arange(nw, device=dev), wi.win_count[:nw].long())
+            v_win = 1.0 + ((win_of[:, None] * 2654435761 + torch.arange(c, device=dev)[None, :] * 97) % 4096).float() / 4096.0
+            with torch.no_grad():
+                out = ops.window_attention_packed(qk, v_win, tau, 0.01, 8, wi)
+            assert float((out - v_win).abs().max()) <= 1e-4
             v = torch.randn(m, c, device=dev, requires_grad=True)
             o = ops.window_attention_packed(qk, v, tau, 0.01, 8, wi)
             g = torch.randn_like(o)
