@@ -734,6 +734,124 @@ int seg3d_softmax_accumulate_f32(const float* logits, int64_t n_points, int32_t 
 int seg3d_argmax_confusion(const float* scores, const int64_t* pred_in, int64_t n_points, int32_t c, int32_t n_views,
                            const void* labels, int32_t label_bytes, int64_t* pred, int64_t* hist, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training augmentation (csrc/augment.hip): what the reference does once per training frame between the disk and the
+ * voxelizer -- PolarMix (seg3d/datasets/transforms/polarmix.py:4-111, called at seg3d/datasets/waymo_dataset.py:307-323)
+ * and the composed transforms (transforms.py:79-258, transform_utils.py:11-138, composed at waymo_dataset.py:44-50).
+ * Every stage selects / reorders rows or maps x, y, z of a row, so the stages build an int32 SOURCE MAP and one kernel
+ * touches the rows.  A source row s addresses the concatenation [frame1; frame2] (s < n1: frame1[s], else
+ * frame2[s - n1]); the frames are never concatenated in memory.  Device entries neither allocate nor synchronise; every
+ * *_host twin takes HOST pointers, is plain C++ without a HIP call (runs in a DataLoader worker or on a machine without
+ * a GPU) and gives the same bits / the same integers as its device entry.
+ */
+#define SEG3D_AUG_MAX_PASTE 8
+typedef struct {
+  double paste_cos[SEG3D_AUG_MAX_PASTE]; /* np.cos / np.sin of PolarMix's rot_angle_range (polarmix.py:48-51) */
+  double paste_sin[SEG3D_AUG_MAX_PASTE];
+  double offset[3];       /* RandomGlobalTranslation's three float64 draws (transform_utils.py:68-94) */
+  float rot_cos, rot_sin; /* torch.cos / torch.sin of the float32 angle (transform_utils.py:21-22) */
+  float scale;            /* float32(noise_scale) (transforms.py:86-87); 1 when the transform is skipped (:84-85) */
+  int32_t n_paste;        /* angles in use, 0 .. 8 */
+  int32_t flip_x, flip_y; /* 0 / 1: random_flip_along_x / _y */
+  int32_t global_on;      /* 0: stop after the float32 rounding (PolarMix alone); 1: the whole chain */
+  int32_t batch_col;      /* 1: out rows are [batch_id, row] (WaymoDataset.collate_batch, waymo_dataset.py:347-352) */
+  float batch_id;
+} seg3d_aug_params;
+
+/* seg3d_aug_polarmix_map -- PolarMix.__call__ (polarmix.py:72-111) as a row map.  points1 [n1, dim], points2 [n2, dim]
+ * float32 (point_bytes 4) or float64 (8), 3 <= dim <= 16; labels2 [n2] uint8 (label_bytes 1) or int64 (8).
+ * Rows, in the reference's order:
+ *   frame-1 rows NOT in the sector, then frame-2 rows in the sector (swap, :4-25; with swap = 0 all of frame 1 and
+ *   nothing of frame 2), both in original order; sector test yaw = -atan2(y, x) in double, yaw > alpha && yaw < beta;
+ *   then the instance block of frame 2 -- class-major in the order of instance_classes (host uint8[n_classes], no class
+ *   twice), ascending row inside a class (:31-41) -- written 1 + n_paste times: op 0, then op 1 .. n_paste (:44-58).
+ * src [cap] int32 / op [cap] uint8 (0 = copy, r = rotate by paste angle r); cap >= n1 + n2 * (2 + n_paste).
+ * counts: int32[4] = {n_out, rows before the instance block, rows of one instance block, 0} (device memory for the
+ * device entry: the caller reads it once, as it reads the voxel count of seg3d_voxelize_f32).  flags -> scan -> emit;
+ * the class-major order from a per-block class histogram, a scan and a stable in-block rank: no sort, no float atomics. */
+size_t seg3d_aug_polarmix_workspace_bytes(int64_t n1, int64_t n2);
+int seg3d_aug_polarmix_map(const void* points1, int64_t n1, const void* points2, int64_t n2, int32_t dim,
+                           int32_t point_bytes, const void* labels2, int32_t label_bytes, int32_t swap, double alpha,
+                           double beta, const uint8_t* instance_classes, int32_t n_classes, int32_t n_paste, int64_t cap,
+                           int32_t* src, uint8_t* op, int32_t* counts, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int seg3d_aug_polarmix_map_host(const void* points1, int64_t n1, const void* points2, int64_t n2, int32_t dim,
+                                int32_t point_bytes, const void* labels2, int32_t label_bytes, int32_t swap, double alpha,
+                                double beta, const uint8_t* instance_classes, int32_t n_classes, int32_t n_paste,
+                                int64_t cap, int32_t* src, uint8_t* op, int32_t* counts);
+
+/* seg3d_aug_far_near -- the far / near lists points_random_sampling draws from (transform_utils.py:120-134).  Row i of
+ * the transformed, shuffled frame is source row src[idx[i]] with op[idx[i]] (idx NULL: i itself; src NULL: the identity
+ * map over n_map <= n1 + n2 rows; op NULL: copies); its x, y go through the recipe of seg3d_aug_apply_f32 and
+ * dist = sqrt(x*x + y*y) in float32 (two rounded products, a rounded sum, IEEE sqrt: np.linalg.norm, :122) is tested
+ * dist >= sample_range.  far_flag [n] uint8 (nullable); far_idx / near_idx [n] int32 (both or neither): the rows i with
+ * and without the flag, ascending, counts int32[2] = {n_far, n_near}.  The workspace is needed for the lists only. */
+size_t seg3d_aug_far_near_workspace_bytes(int64_t n);
+int seg3d_aug_far_near(const void* frame1, int64_t n1, const void* frame2, int64_t n2, int32_t dim, int32_t point_bytes,
+                       const int32_t* src, const uint8_t* op, int64_t n_map, const int32_t* idx, int64_t n,
+                       const seg3d_aug_params* params /* host */, float sample_range, uint8_t* far_flag, int32_t* far_idx,
+                       int32_t* near_idx, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int seg3d_aug_far_near_host(const void* frame1, int64_t n1, const void* frame2, int64_t n2, int32_t dim, int32_t point_bytes,
+                            const int32_t* src, const uint8_t* op, int64_t n_map, const int32_t* idx, int64_t n,
+                            const seg3d_aug_params* params, float sample_range, uint8_t* far_flag, int32_t* far_idx,
+                            int32_t* near_idx, int32_t* counts);
+
+/* seg3d_aug_sample_device -- PointShuffle + PointSample (transforms.py:141-146, :211-217, transform_utils.py:117-134)
+ * without host random numbers: out [n_samples] = distinct rows of [0, n), far rows (far_flag != 0; NULL = none) kept
+ * before near rows, a uniform subset of the set that does not fit, in uniform order -- the reference's distribution,
+ * not its draws.  Keys are a counter-based hash of (seed, stream, row) with the row in the low 32 bits (unique keys):
+ * one radix sort on (near bit, hash) selects, one on a fresh hash orders.  A pure function of (seed, n, far_flag);
+ * the host twin sorts the same keys. */
+size_t seg3d_aug_sample_workspace_bytes(int64_t n);
+int seg3d_aug_sample_device(const uint8_t* far_flag, int64_t n, int64_t n_samples, uint64_t seed, int32_t* out,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int seg3d_aug_sample_host(const uint8_t* far_flag, int64_t n, int64_t n_samples, uint64_t seed, int32_t* out);
+
+/* seg3d_aug_cur_map -- PointShuffle / PointSample.get_shuffled_indices (transforms.py:165-177, :237-249), both dict
+ * loops at once: src [m] = source point of every output row, cur_point_indices [n_cur] = the points of the current
+ * sweep among n_points (a point listed twice keeps its later slot, as the dict does).  cur_pos [<= m] = the output rows
+ * whose source is a current-sweep point, ascending (the new cur_point_indices); cur_gather = that point's slot (the
+ * gather list for labels and image features, which are sized to the current sweep, :152-161, :224-233);
+ * count int32[1]. */
+size_t seg3d_aug_cur_map_workspace_bytes(int64_t m, int64_t n_points);
+int seg3d_aug_cur_map(const int32_t* src, int64_t m, const int32_t* cur_point_indices, int64_t n_cur, int64_t n_points,
+                      int32_t* cur_pos, int32_t* cur_gather, int32_t* count, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int seg3d_aug_cur_map_host(const int32_t* src, int64_t m, const int32_t* cur_point_indices, int64_t n_cur, int64_t n_points,
+                           int32_t* cur_pos, int32_t* cur_gather, int32_t* count);
+
+/* seg3d_aug_apply_f32 / _f64in -- the rows themselves, each source row read once and each output row written once:
+ * out [n_out, dim] float32 (or [n_out, 1 + dim] with params->batch_col).  Per output row g, source src[g] (NULL: g),
+ * op[g] (NULL: 0), without fused multiply-add:
+ *   1. op = r > 0: x' = x*cos_r + y*(-sin_r), y' = x*sin_r + y*cos_r in DOUBLE (np.dot, polarmix.py:48-53)
+ *   2. x, y, z and the other columns rounded to float32 (the .float() of transform_utils.py:7)
+ *   3. x' = x*c + y*(-s), y' = x*s + y*c in float32 (points @ [[c, s, 0], [-s, c, 0], [0, 0, 1]], :25-30)
+ *   4. xyz *= scale (transforms.py:87)
+ *   5. x = float32(double(x) + offset[0]), likewise y, z (numpy adds the float64 draw in double, :69, :81, :93)
+ *   6. flip_x: y = -y, then flip_y: x = -x (:35-58)
+ * (3-6 only with params->global_on).  A source outside [0, n1 + n2) reads as a row of zeros.  `params` is a HOST
+ * pointer; the kernel receives it by value.  dim outside [3, 16]: SEG3D_EINVAL. */
+int seg3d_aug_apply_f32(const float* frame1, int64_t n1, const float* frame2, int64_t n2, int32_t dim, const int32_t* src,
+                        const uint8_t* op, int64_t n_out, const seg3d_aug_params* params, float* out, void* stream);
+int seg3d_aug_apply_f64in(const double* frame1, int64_t n1, const double* frame2, int64_t n2, int32_t dim,
+                          const int32_t* src, const uint8_t* op, int64_t n_out, const seg3d_aug_params* params, float* out,
+                          void* stream);
+int seg3d_aug_apply_host_f32(const float* frame1, int64_t n1, const float* frame2, int64_t n2, int32_t dim,
+                             const int32_t* src, const uint8_t* op, int64_t n_out, const seg3d_aug_params* params,
+                             float* out);
+int seg3d_aug_apply_host_f64in(const double* frame1, int64_t n1, const double* frame2, int64_t n2, int32_t dim,
+                               const int32_t* src, const uint8_t* op, int64_t n_out, const seg3d_aug_params* params,
+                               float* out);
+
+/* seg3d_aug_gather -- labels, image features and composed maps through a map (polarmix.py:17-22, :33-36;
+ * transforms.py:157-161, :229-233): out row g = row idx[g] of the concatenation [a (na rows); b (nb rows)] of rows of
+ * row_bytes bytes (1 for uint8 labels, 8 for int64, 4 * F for features, 4 for an int32 map: src2 = src[perm][choices]),
+ * zeros for an index outside it.  16-byte accesses when pointers and row_bytes allow. */
+int seg3d_aug_gather(const void* a, int64_t na, const void* b, int64_t nb, int64_t row_bytes, const int32_t* idx, int64_t m,
+                     void* out, void* stream);
+int seg3d_aug_gather_host(const void* a, int64_t na, const void* b, int64_t nb, int64_t row_bytes, const int32_t* idx,
+                          int64_t m, void* out);
+
 #ifdef __cplusplus
 }
 #endif

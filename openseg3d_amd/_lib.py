@@ -13,10 +13,11 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 42
+ABI_VERSION = 43
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
+_d = ctypes.c_double
 
 # name -> (restype, argtypes); must match include/seg3d_hip.h (tests/test_boundary.py cross-checks the names)
 SIGNATURES = {
@@ -127,6 +128,28 @@ SIGNATURES = {
     "seg3d_tta_views_host_f32": (ctypes.c_int, [_p, _i64, _i32, _p, _p]),
     "seg3d_softmax_accumulate_f32": (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p]),
     "seg3d_argmax_confusion": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _p, _i32, _p, _p, _p]),
+    "seg3d_aug_polarmix_workspace_bytes": (_sz, [_i64, _i64]),
+    "seg3d_aug_polarmix_map": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _i32, _p, _i32, _i32, _d, _d, _p, _i32, _i32, _i64,
+                                              _p, _p, _p, _p, _sz, _p]),
+    "seg3d_aug_polarmix_map_host": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _i32, _p, _i32, _i32, _d, _d, _p, _i32, _i32,
+                                                   _i64, _p, _p, _p]),
+    "seg3d_aug_far_near_workspace_bytes": (_sz, [_i64]),
+    "seg3d_aug_far_near": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _i64, _p, _f, _p, _p, _p, _p,
+                                          _p, _sz, _p]),
+    "seg3d_aug_far_near_host": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _i32, _p, _p, _i64, _p, _i64, _p, _f, _p, _p, _p,
+                                               _p]),
+    "seg3d_aug_sample_workspace_bytes": (_sz, [_i64]),
+    "seg3d_aug_sample_device": (ctypes.c_int, [_p, _i64, _i64, _u64, _p, _p, _sz, _p]),
+    "seg3d_aug_sample_host": (ctypes.c_int, [_p, _i64, _i64, _u64, _p]),
+    "seg3d_aug_cur_map_workspace_bytes": (_sz, [_i64, _i64]),
+    "seg3d_aug_cur_map": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
+    "seg3d_aug_cur_map_host": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _p, _p, _p]),
+    "seg3d_aug_apply_f32": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _p, _p]),
+    "seg3d_aug_apply_f64in": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _p, _p]),
+    "seg3d_aug_apply_host_f32": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _p]),
+    "seg3d_aug_apply_host_f64in": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _p]),
+    "seg3d_aug_gather": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p, _p]),
+    "seg3d_aug_gather_host": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p]),
 }
 
 _ERR = {EINVAL: "SEG3D_EINVAL (bad argument)", EWORKSPACE: "SEG3D_EWORKSPACE (workspace too small)",

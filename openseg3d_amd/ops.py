@@ -2456,3 +2456,274 @@ def argmax_confusion(scores=None, n_classes=None, pred_in=None, labels=None, his
     _lib.call("seg3d_argmax_confusion", _ptr(scores), _ptr(pred_in), n, c, int(n_views), _ptr(labels), lb, _ptr(pred),
               _ptr(hist), _stream())
     return pred
+
+
+# ------------------------------------------------------------------------------------------ training augmentation (csrc/augment.hip)
+AUG_MAX_PASTE = 8
+
+
+class AugParams(ctypes.Structure):
+    """seg3d_aug_params (include/seg3d_hip.h): the per-row recipe of seg3d_aug_apply_f32."""
+    _fields_ = [("paste_cos", ctypes.c_double * AUG_MAX_PASTE), ("paste_sin", ctypes.c_double * AUG_MAX_PASTE),
+                ("offset", ctypes.c_double * 3), ("rot_cos", ctypes.c_float), ("rot_sin", ctypes.c_float),
+                ("scale", ctypes.c_float), ("n_paste", ctypes.c_int32), ("flip_x", ctypes.c_int32),
+                ("flip_y", ctypes.c_int32), ("global_on", ctypes.c_int32), ("batch_col", ctypes.c_int32),
+                ("batch_id", ctypes.c_float)]
+
+
+def aug_params(paste_angles=(), rot_angle=None, scale=1.0, offsets=(0.0, 0.0, 0.0), flip_x=False, flip_y=False,
+               batch_id=None):
+    """The constants of one frame's augmentation.  paste_angles: PolarMix's rot_angle_range, cos / sin taken in float64
+    as polarmix.py:48-51 does; rot_angle: RandomGlobalRotation's draw -- cast to float32, torch.cos / torch.sin on the
+    CPU, as transform_utils.py:7, :21-22 (None: the global transforms are left out, PolarMix alone); scale:
+    numpy's `points[:, :3] *= noise_scale` on float32 rows multiplies by float32(scale) (transforms.py:87); offsets: the
+    three float64 translation draws; batch_id: not None writes collated rows [batch_id, row]."""
+    if len(paste_angles) > AUG_MAX_PASTE:
+        raise _lib.Seg3dError(f"{len(paste_angles)} paste angles: the kernels take at most {AUG_MAX_PASTE}")
+    p = AugParams()
+    p.n_paste = len(paste_angles)
+    for r, a in enumerate(paste_angles):
+        p.paste_cos[r], p.paste_sin[r] = float(np.cos(a)), float(np.sin(a))
+    p.global_on = int(rot_angle is not None)
+    ang = torch.tensor([0.0 if rot_angle is None else float(rot_angle)], dtype=torch.float64).float()
+    p.rot_cos, p.rot_sin = float(torch.cos(ang)[0]), float(torch.sin(ang)[0])
+    p.scale = float(np.float32(scale))
+    for j in range(3):
+        p.offset[j] = float(offsets[j])
+    p.flip_x, p.flip_y = int(bool(flip_x)), int(bool(flip_y))
+    p.batch_col, p.batch_id = int(batch_id is not None), float(batch_id or 0)
+    return p
+
+
+def _hp(a):
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def _aug_frames(frame1, frame2, host):
+    """Both frames contiguous [n, D] of one float dtype (frame2 may be None) -> (f1, f2, n1, n2, D, point_bytes)."""
+    f32, f64 = (np.float32, np.float64) if host else (torch.float32, torch.float64)
+    if host:
+        frame1 = np.ascontiguousarray(frame1)
+        frame2 = None if frame2 is None else np.ascontiguousarray(frame2)
+    else:
+        _need_gpu(frame1, frame2)
+        frame1 = frame1.contiguous()
+        frame2 = None if frame2 is None else frame2.contiguous()
+    if frame1.ndim != 2 or frame1.dtype not in (f32, f64):
+        raise _lib.Seg3dError("points must be a float32/float64 [N, D] array")
+    if frame2 is not None and (frame2.ndim != 2 or frame2.dtype != frame1.dtype or frame2.shape[1] != frame1.shape[1]):
+        raise _lib.Seg3dError("both frames must have the same float dtype and the same number of columns")
+    d = int(frame1.shape[1])
+    if not 3 <= d <= 16:
+        raise _lib.Seg3dError(f"points have {d} columns: the augmentation kernels take 3 .. 16")
+    return frame1, frame2, int(frame1.shape[0]), 0 if frame2 is None else int(frame2.shape[0]), d, \
+        4 if frame1.dtype == f32 else 8
+
+
+def _aug_labels(labels, host):
+    u8, i64 = (np.uint8, np.int64) if host else (torch.uint8, torch.int64)
+    if labels.dtype not in (u8, i64) or labels.ndim != 1:
+        raise _lib.Seg3dError("labels must be a uint8 or int64 [N] array")
+    return (np.ascontiguousarray(labels) if host else labels.contiguous()), (1 if labels.dtype == u8 else 8)
+
+
+def _aug_classes(instance_classes):
+    cls = [int(c) for c in instance_classes]
+    if any(c < 0 or c > 255 for c in cls) or len(set(cls)) != len(cls):
+        raise _lib.Seg3dError("instance_classes must be distinct labels in 0 .. 255")
+    return (ctypes.c_uint8 * max(len(cls), 1))(*cls), len(cls)
+
+
+def polarmix_map(points1, points2, labels2, swap, alpha, beta, instance_classes, n_paste):
+    """seg3d_aug_polarmix_map: PolarMix as a row map.  CUDA points1 [n1, D], points2 [n2, D], labels2 [n2] ->
+    (src int32 [n_out], op uint8 [n_out], n_before_instances, n_instances).  One host sync (reads the counts)."""
+    p1, p2, n1, n2, d, pb = _aug_frames(points1, points2, False)
+    _need_gpu(labels2)
+    lab, lb = _aug_labels(labels2, False)
+    if lab.numel() != n2:
+        raise _lib.Seg3dError(f"{lab.numel()} labels for {n2} points")
+    cls, nc = _aug_classes(instance_classes)
+    dev = p1.device
+    cap = n1 + n2 * (2 + int(n_paste))
+    src = torch.empty((cap,), dtype=torch.int32, device=dev)
+    op = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    counts = torch.zeros((4,), dtype=torch.int32, device=dev)
+    ws = _workspace(_lib.query("seg3d_aug_polarmix_workspace_bytes", n1, n2), dev)
+    _lib.call("seg3d_aug_polarmix_map", _ptr(p1), n1, _ptr(p2), n2, d, pb, _ptr(lab), lb, int(bool(swap)), float(alpha),
+              float(beta), cls, nc, int(n_paste), cap, _ptr(src), _ptr(op), _ptr(counts), _ptr(ws), ws.numel(), _stream())
+    n_out, base, n_inst, _ = counts.tolist()
+    return src[:n_out], op[:n_out], base, n_inst
+
+
+def polarmix_map_host(points1, points2, labels2, swap, alpha, beta, instance_classes, n_paste):
+    """seg3d_aug_polarmix_map_host: the same map from numpy arrays; no HIP call."""
+    p1, p2, n1, n2, d, pb = _aug_frames(points1, points2, True)
+    lab, lb = _aug_labels(np.asarray(labels2), True)
+    if lab.size != n2:
+        raise _lib.Seg3dError(f"{lab.size} labels for {n2} points")
+    cls, nc = _aug_classes(instance_classes)
+    cap = n1 + n2 * (2 + int(n_paste))
+    src = np.empty((cap,), dtype=np.int32)
+    op = np.empty((cap,), dtype=np.uint8)
+    counts = np.zeros((4,), dtype=np.int32)
+    _lib.call("seg3d_aug_polarmix_map_host", _hp(p1), n1, _hp(p2), n2, d, pb, _hp(lab), lb, int(bool(swap)),
+              float(alpha), float(beta), cls, nc, int(n_paste), cap, _hp(src), _hp(op), _hp(counts))
+    n_out, base, n_inst, _ = counts.tolist()
+    return src[:n_out], op[:n_out], base, n_inst
+
+
+def _aug_map_args(src, op, idx, n1, n2, host):
+    i32, u8 = (np.int32, np.uint8) if host else (torch.int32, torch.uint8)
+    for name, a, dt in (("src", src, i32), ("op", op, u8), ("idx", idx, i32)):
+        if a is not None and (a.dtype != dt or a.ndim != 1):
+            raise _lib.Seg3dError(f"{name} must be a 1-d {dt} array")
+    if op is not None and (src is None or op.shape[0] != src.shape[0]):
+        raise _lib.Seg3dError("op needs a src map of the same length")
+    c = (lambda a: None if a is None else np.ascontiguousarray(a)) if host else \
+        (lambda a: None if a is None else a.contiguous())
+    n_map = n1 + n2 if src is None else int(src.shape[0])
+    return c(src), c(op), c(idx), n_map
+
+
+def aug_far_near(frame1, frame2, src, op, idx, params, sample_range, lists=True):
+    """seg3d_aug_far_near on CUDA tensors.  lists=True: (far_idx, near_idx) int32, trimmed -- one host sync (reads the
+    two counts); lists=False: the uint8 far flag of every row, no sync."""
+    f1, f2, n1, n2, d, pb = _aug_frames(frame1, frame2, False)
+    _need_gpu(src, op, idx)
+    src, op, idx, n_map = _aug_map_args(src, op, idx, n1, n2, False)
+    n = n_map if idx is None else int(idx.shape[0])
+    dev = f1.device
+    if not lists:
+        flag = torch.empty((n,), dtype=torch.uint8, device=dev)
+        _lib.call("seg3d_aug_far_near", _ptr(f1), n1, _ptr(f2), n2, d, pb, _ptr(src), _ptr(op), n_map, _ptr(idx), n,
+                  ctypes.byref(params), float(sample_range), _ptr(flag), None, None, None, None, 0, _stream())
+        return flag
+    far = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    near = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    counts = torch.zeros((2,), dtype=torch.int32, device=dev)
+    ws = _workspace(_lib.query("seg3d_aug_far_near_workspace_bytes", n), dev)
+    _lib.call("seg3d_aug_far_near", _ptr(f1), n1, _ptr(f2), n2, d, pb, _ptr(src), _ptr(op), n_map, _ptr(idx), n,
+              ctypes.byref(params), float(sample_range), None, _ptr(far), _ptr(near), _ptr(counts), _ptr(ws), ws.numel(),
+              _stream())
+    nf, nn = counts.tolist()
+    return far[:nf], near[:nn]
+
+
+def aug_far_near_host(frame1, frame2, src, op, idx, params, sample_range, lists=True):
+    """seg3d_aug_far_near_host: numpy in, numpy out; no HIP call."""
+    f1, f2, n1, n2, d, pb = _aug_frames(frame1, frame2, True)
+    src, op, idx, n_map = _aug_map_args(src, op, idx, n1, n2, True)
+    n = n_map if idx is None else int(idx.shape[0])
+    flag = np.empty((n,), dtype=np.uint8)
+    far = np.empty((max(n, 1),), dtype=np.int32)
+    near = np.empty((max(n, 1),), dtype=np.int32)
+    counts = np.zeros((2,), dtype=np.int32)
+    _lib.call("seg3d_aug_far_near_host", _hp(f1), n1, _hp(f2), n2, d, pb, _hp(src), _hp(op), n_map, _hp(idx), n,
+              ctypes.byref(params), float(sample_range), _hp(flag), _hp(far), _hp(near), _hp(counts))
+    return (far[:counts[0]], near[:counts[1]]) if lists else flag
+
+
+def aug_sample_device(far_flag, n, n_samples, seed, device=None):
+    """seg3d_aug_sample_device: n_samples distinct rows of [0, n), far rows first, in hashed order; no host sync."""
+    _need_gpu(far_flag)
+    if far_flag is not None and (far_flag.dtype != torch.uint8 or far_flag.numel() != n):
+        raise _lib.Seg3dError("far_flag must be a uint8 [n] tensor")
+    dev = far_flag.device if far_flag is not None else torch.device(device or "cuda")
+    out = torch.empty((int(n_samples),), dtype=torch.int32, device=dev)
+    if n_samples:
+        ws = _workspace(_lib.query("seg3d_aug_sample_workspace_bytes", int(n)), dev)
+        _lib.call("seg3d_aug_sample_device", _ptr(None if far_flag is None else far_flag.contiguous()), int(n),
+                  int(n_samples), int(seed) & (2 ** 64 - 1), _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
+def aug_sample_host(far_flag, n, n_samples, seed):
+    """seg3d_aug_sample_host: the same rows from the same keys, sorted on the host."""
+    if far_flag is not None:
+        far_flag = np.ascontiguousarray(far_flag, dtype=np.uint8)
+        if far_flag.size != n:
+            raise _lib.Seg3dError("far_flag must be a uint8 [n] array")
+    out = np.empty((int(n_samples),), dtype=np.int32)
+    _lib.call("seg3d_aug_sample_host", _hp(far_flag), int(n), int(n_samples), int(seed) & (2 ** 64 - 1), _hp(out))
+    return out
+
+
+def aug_cur_map(src, cur_point_indices, n_points):
+    """seg3d_aug_cur_map: (cur_pos, cur_gather) int32 of a source map and the current-sweep points.  One host sync."""
+    _need_gpu(src, cur_point_indices)
+    src, cur = _i32c(src), _i32c(cur_point_indices)
+    m, dev = int(src.shape[0]), src.device
+    pos = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
+    gat = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
+    count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    ws = _workspace(_lib.query("seg3d_aug_cur_map_workspace_bytes", m, int(n_points)), dev)
+    _lib.call("seg3d_aug_cur_map", _ptr(src), m, _ptr(cur), int(cur.shape[0]), int(n_points), _ptr(pos), _ptr(gat),
+              _ptr(count), _ptr(ws), ws.numel(), _stream())
+    k = int(count.item())
+    return pos[:k], gat[:k]
+
+
+def aug_cur_map_host(src, cur_point_indices, n_points):
+    """seg3d_aug_cur_map_host: numpy in, numpy out; no HIP call."""
+    src = np.ascontiguousarray(src, dtype=np.int32)
+    cur = np.ascontiguousarray(cur_point_indices, dtype=np.int32)
+    m = int(src.shape[0])
+    pos = np.empty((max(m, 1),), dtype=np.int32)
+    gat = np.empty((max(m, 1),), dtype=np.int32)
+    count = np.zeros((1,), dtype=np.int32)
+    _lib.call("seg3d_aug_cur_map_host", _hp(src), m, _hp(cur), int(cur.shape[0]), int(n_points), _hp(pos), _hp(gat),
+              _hp(count))
+    return pos[:count[0]], gat[:count[0]]
+
+
+def aug_apply(frame1, frame2, src, op, params):
+    """seg3d_aug_apply_f32 / _f64in: the augmented float32 rows [n_out, D] (or [n_out, 1 + D] with a batch id in the
+    parameters) of CUDA frames through a source map; one launch, every row read and written once."""
+    f1, f2, n1, n2, d, pb = _aug_frames(frame1, frame2, False)
+    _need_gpu(src, op)
+    src, op, _, n_out = _aug_map_args(src, op, None, n1, n2, False)
+    out = torch.empty((n_out, d + params.batch_col), dtype=torch.float32, device=f1.device)
+    _lib.call("seg3d_aug_apply_f32" if pb == 4 else "seg3d_aug_apply_f64in", _ptr(f1), n1, _ptr(f2), n2, d, _ptr(src),
+              _ptr(op), n_out, ctypes.byref(params), _ptr(out), _stream())
+    return out
+
+
+def aug_apply_host(frame1, frame2, src, op, params):
+    """seg3d_aug_apply_host_f32 / _f64in: the same rows on the host (numpy in, numpy out); no HIP call."""
+    f1, f2, n1, n2, d, pb = _aug_frames(frame1, frame2, True)
+    src, op, _, n_out = _aug_map_args(src, op, None, n1, n2, True)
+    out = np.empty((n_out, d + params.batch_col), dtype=np.float32)
+    _lib.call("seg3d_aug_apply_host_f32" if pb == 4 else "seg3d_aug_apply_host_f64in", _hp(f1), n1, _hp(f2), n2, d,
+              _hp(src), _hp(op), n_out, ctypes.byref(params), _hp(out))
+    return out
+
+
+def aug_gather(a, b, idx):
+    """seg3d_aug_gather: rows idx of the concatenation [a; b] (b may be None) of CUDA tensors of one dtype and row
+    shape: labels, image features, or an int32 map composed with another."""
+    _need_gpu(a, b, idx)
+    if idx.dtype != torch.int32 or idx.dim() != 1 or (b is not None and (b.dtype != a.dtype or b.shape[1:] != a.shape[1:])):
+        raise _lib.Seg3dError("aug_gather: an int32 index and two sources of one dtype and row shape")
+    a, idx = a.contiguous(), idx.contiguous()
+    b = None if b is None else b.contiguous()
+    m = int(idx.shape[0])
+    out = torch.empty((m,) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+    row_bytes = a.element_size() * int(np.prod(a.shape[1:], dtype=np.int64))
+    _lib.call("seg3d_aug_gather", _ptr(a), int(a.shape[0]), _ptr(b), 0 if b is None else int(b.shape[0]), row_bytes,
+              _ptr(idx), m, _ptr(out), _stream())
+    return out
+
+
+def aug_gather_host(a, b, idx):
+    """seg3d_aug_gather_host: numpy in, numpy out; no HIP call."""
+    a = np.ascontiguousarray(a)
+    b = None if b is None else np.ascontiguousarray(b)
+    idx = np.ascontiguousarray(idx)
+    if idx.dtype != np.int32 or idx.ndim != 1 or (b is not None and (b.dtype != a.dtype or b.shape[1:] != a.shape[1:])):
+        raise _lib.Seg3dError("aug_gather: an int32 index and two sources of one dtype and row shape")
+    m = int(idx.shape[0])
+    out = np.empty((m,) + tuple(a.shape[1:]), dtype=a.dtype)
+    row_bytes = a.itemsize * int(np.prod(a.shape[1:], dtype=np.int64))
+    _lib.call("seg3d_aug_gather_host", _hp(a), int(a.shape[0]), _hp(b), 0 if b is None else int(b.shape[0]), row_bytes,
+              _hp(idx), m, _hp(out))
+    return out
