@@ -852,6 +852,81 @@ int seg3d_aug_gather(const void* a, int64_t na, const void* b, int64_t nb, int64
 int seg3d_aug_gather_host(const void* a, int64_t na, const void* b, int64_t nb, int64_t row_bytes, const int32_t* idx,
                           int64_t m, void* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Instance copy-paste augmentation (csrc/augment_instance.hip): InstanceAugmentation.__call__
+ * (seg3d/datasets/transforms/instance_augmentation.py:25-107, called at waymo_dataset.py:314-315, :321) without its
+ * random draws, which are independent of the data and arrive in the plans.
+ *
+ * seg3d_aug_instance_plan -- one instance to paste, a HOST struct (the kernels receive it by value):
+ *   row_begin, n_rows   its rows in the packed bank (`cluster_points`, :47-48); n_rows >= 1
+ *   label               the label its rows get (:97), 0 .. 255
+ *   height              `cluster_height` (:49)
+ *   local_on            1: local_transform (:57-58, :166-177) with loc_noise (normal(scale=0.25), :169) and
+ *                       rot_cos / rot_sin = np.cos / np.sin of rot_noise (uniform(-pi/20, pi/20), :171)
+ *   flip                1: flip_type == 3 was drawn (:66-69), the flip over the short axis through the PRE-transform
+ *                       centre (:63-64, :121-127); every other flip_type does nothing in the reference
+ *   n_angles            candidate rotations (:77), 0 .. SEG3D_AUG_MAX_ANGLES, in draw order, with
+ *   ang_cos / ang_sin   np.cos / np.sin of each
+ */
+#define SEG3D_AUG_MAX_ANGLES 20
+typedef struct {
+  int64_t row_begin;
+  int32_t n_rows;
+  int32_t label;
+  double height;
+  double loc_noise[3];
+  double rot_cos, rot_sin;
+  int32_t local_on;
+  int32_t flip;
+  int32_t n_angles;
+  int32_t reserved;
+  double ang_cos[SEG3D_AUG_MAX_ANGLES];
+  double ang_sin[SEG3D_AUG_MAX_ANGLES];
+} seg3d_aug_instance_plan;
+
+/* seg3d_aug_instance_paste -- the k planned instances, one after the other; instance i is checked against the frame
+ * plus the rows instances 0 .. i-1 pasted (:35-45 are re-run per instance in the reference).
+ * In:  points [n, dim] float32 (point_bytes 4) or float64 (8), converted exactly to double, 3 <= dim <= 16 (outside:
+ *      SEG3D_EINVAL); labels [n] uint8 (label_bytes 1) or int64 (8); ground_ids host uint8 [n_ground]: rows with label
+ *      255 are skipped, rows with a ground label are ground points, all other rows -- pasted ones included -- are
+ *      object points (:38-43); bank double [bank_rows, dim], device memory for the device entry: xyz and the feature
+ *      columns as they are pasted (the caller applies :52-53 once when it packs the bank); plans host [k].
+ * Per instance, all in double and without fused multiply-add (IEEE add / mul / div / sqrt / compare only):
+ *   center0 = mean(xyz) (:56); xyz = rotate_origin(xyz - center0) + loc_noise + center0 (local_on); flip about center0;
+ *   center = mean(xyz), radius = max ||xyz - center|| (:73-74).  Both means in one fixed order: partial sum t adds rows
+ *   t, t + 256, ..., then the 256 partial sums fold by halving.  Per candidate r, in order: c = rotate_origin(center, r)
+ *   (x' = x cos + y sin, y' = -x sin + y cos, :157-164), d = sqrt((dx*dx + dy*dy) + dz*dz) to every row;
+ *   no_occlusion = no object row with d <= radius (:138); on_ground = the smallest ground d < 1.2 * radius (:145).  The
+ *   first candidate with both wins (:78-84); ground_z = z of the ground row with the smallest d, LOWEST ROW on equal d
+ *   (np.argmin, :149); z += (ground_z + height) - center_z (:150-152); then rotate_origin by r (:87).  No candidate
+ *   wins: nothing is appended (:86).  No ground row: nothing can be placed (the reference raises at :45); no object
+ *   row: no_occlusion holds.
+ * Out: add_points double [cap_add, dim] / add_labels [cap_add] in the labels' own width: the accepted instances' rows
+ *      [xyz, bank columns 3 ..] in processing order (:95-98); cap_add >= the sum of the plans' n_rows, otherwise
+ *      SEG3D_EINVAL.  decisions int32 [k]: the accepted candidate index or -1.  counts int32 [4] = {rows added,
+ *      instances placed, 0, 0}; device memory for the device entry, which the caller reads once (counts[0] is also the
+ *      running row count the kernels read: the host cannot know whether instance i-1 was accepted).  The frame's own
+ *      rows are not copied: the result frame is [points; add_points[:counts[0]]].
+ * Device: 2 k + 1 launches -- step(0) scan(0) step(1) ... scan(k-1) step(k); scan(i): one pass over the rows for all
+ * candidates of instance i at once (per candidate an occluded bit and the minimum (d, row), wave64 shuffles -> LDS ->
+ * one record per workgroup; the candidate centres are read from the workspace, where step(i) left them, through
+ * uniform loads); step(i): one workgroup that folds the records, decides and appends instance i-1 and prepares
+ * instance i.  No allocation, no host synchronisation, no float atomics; (d, row) minima and ORs are exact, so the
+ * result does not depend on the launch geometry.  The *_host twin takes host pointers, makes no HIP call and returns
+ * the same bits and the same integers.  workspace_bytes: sized by max_instance_rows = the largest n_rows of the plans
+ * (n and k are accepted for the caller's convenience and do not change the size: the grid, hence the record list, is
+ * capped, and instance i reuses the buffers of instance i-2). */
+size_t seg3d_aug_instance_workspace_bytes(int64_t n, int64_t max_instance_rows, int32_t k);
+int seg3d_aug_instance_paste(const void* points, int64_t n, int32_t dim, int32_t point_bytes, const void* labels,
+                             int32_t label_bytes, const uint8_t* ground_ids, int32_t n_ground, const double* bank,
+                             int64_t bank_rows, const seg3d_aug_instance_plan* plans, int32_t k, int64_t cap_add,
+                             double* add_points, void* add_labels, int32_t* decisions, int32_t* counts, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int seg3d_aug_instance_paste_host(const void* points, int64_t n, int32_t dim, int32_t point_bytes, const void* labels,
+                                  int32_t label_bytes, const uint8_t* ground_ids, int32_t n_ground, const double* bank,
+                                  int64_t bank_rows, const seg3d_aug_instance_plan* plans, int32_t k, int64_t cap_add,
+                                  double* add_points, void* add_labels, int32_t* decisions, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

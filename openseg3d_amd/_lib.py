@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -150,6 +150,11 @@ SIGNATURES = {
     "seg3d_aug_apply_host_f64in": (ctypes.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _i64, _p, _p]),
     "seg3d_aug_gather": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p, _p]),
     "seg3d_aug_gather_host": (ctypes.c_int, [_p, _i64, _p, _i64, _i64, _p, _i64, _p]),
+    "seg3d_aug_instance_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "seg3d_aug_instance_paste": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _i32, _i64, _p, _p,
+                                                _p, _p, _p, _sz, _p]),
+    "seg3d_aug_instance_paste_host": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _i32, _i64, _p,
+                                                     _p, _p, _p]),
 }
 
 _ERR = {EINVAL: "SEG3D_EINVAL (bad argument)", EWORKSPACE: "SEG3D_EWORKSPACE (workspace too small)",

@@ -1,4 +1,5 @@
-"""Training augmentation: PolarMix, the global transforms, PointShuffle and PointSample (csrc/augment.hip).
+"""Training augmentation: InstanceAugmentation (csrc/augment_instance.hip), PolarMix, the global transforms, PointShuffle
+and PointSample (csrc/augment.hip).
 
 The reference runs these once per training frame on the host, between the disk and the voxelizer
 (seg3d/datasets/transforms/polarmix.py, transforms.py, transform_utils.py; composed at
@@ -12,8 +13,15 @@ PointShuffle permutation and the PointSample choices, and because the far / near
 device this mode has ONE MORE host sync than the other.  ``rng="device"`` draws only the scalars on the host; shuffle
 and sample are sorts of hashed keys on the device: the reference's distribution, not its draws.
 
-Out of scope: ``InstanceAugmentation`` (it needs a pickled instance bank that is not part of this repository) and
-``RandomDropPointsColor`` (no config composes it)."""
+``InstanceAugmentation`` (seg3d/datasets/transforms/instance_augmentation.py, called at waymo_dataset.py:314-315, :321)
+pastes up to ``add_count`` objects of an instance bank into frame 1 before PolarMix.  All of its random numbers are
+independent of the data, so ``draw`` takes them up front, in the reference's call order, and the placement search -- one
+pass over the frame for all candidate rotations of an instance at once -- runs in the library, in double on both paths.
+The bank is the reference's pickled dict; ``InstanceBank`` packs it once.
+
+Out of scope: ``RandomDropPointsColor`` (no config composes it)."""
+import pickle
+
 import numpy as np
 import torch
 
@@ -59,7 +67,8 @@ def _backend(x):
 
 class AugDraw:
     """The parameter record of one frame: every number the reference draws from ``numpy.random`` for it."""
-    __slots__ = ("swap", "alpha", "beta", "rot", "scale", "offsets", "flip_x", "flip_y", "perm", "choices")
+    __slots__ = ("swap", "alpha", "beta", "rot", "scale", "offsets", "flip_x", "flip_y", "perm", "choices",
+                 "instance_draw")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -104,10 +113,154 @@ class PolarMix:
         return points, labels
 
 
+class InstanceBank:
+    """The reference's instance bank, packed once: ``instances`` is its pickled dict ``label_id -> list of
+    {'cluster_points': [m, D], 'cluster_height': float}`` (tools/extract_instances.py:65-76).  ``rows`` float64 [R, D]:
+    every cluster's rows, with feature column 0 zeroed and feature column 1 replaced by its ``np.tanh`` as
+    instance_augmentation.py:52-53 does on every call (in the cluster's own dtype, then converted exactly);
+    ``entries[label]``: (first row, rows, height) per cluster."""
+
+    def __init__(self, instances):
+        self.entries = {}
+        blocks, begin, dim = [], 0, None
+        for label in sorted(instances):
+            self.entries[int(label)] = []
+            for inst in instances[label]:
+                pts = np.array(inst["cluster_points"])  # a copy, as :48
+                if pts.ndim != 2 or pts.shape[0] < 1 or pts.shape[1] < 3 or (dim is not None and pts.shape[1] != dim):
+                    raise Seg3dError("every cluster of an instance bank is [m >= 1, D >= 3] with one D")
+                dim = pts.shape[1]
+                if dim > 3:
+                    pts[:, 3] = 0
+                if dim > 4:
+                    pts[:, 4] = np.tanh(pts[:, 4])
+                blocks.append(pts.astype(np.float64))
+                self.entries[int(label)].append((begin, pts.shape[0], float(inst["cluster_height"])))
+                begin += pts.shape[0]
+        self.dim = dim
+        self.rows = np.concatenate(blocks) if blocks else np.zeros((0, 3))
+        self._device_rows = {}
+
+    @classmethod
+    def from_pickle(cls, path):
+        with open(path, "rb") as f:
+            return cls(pickle.load(f))
+
+    def to(self, device):
+        """Upload the rows once per device; returns the bank itself."""
+        device = torch.device(device)
+        if device not in self._device_rows:
+            self._device_rows[device] = torch.from_numpy(self.rows).to(device)
+        return self
+
+    def rows_on(self, device):
+        return self.to(device)._device_rows[torch.device(device)]
+
+
+class InstanceDraw:
+    """Every number ``InstanceAugmentation`` draws for one frame: per instance, in processing order, ``label``,
+    ``index`` (into the bank's list of that label), ``loc_noise`` [3] and ``rot_noise`` (None without the local
+    transform), ``flip_type`` (None without the flip) and the candidate ``angles``."""
+    __slots__ = ("label", "index", "loc_noise", "rot_noise", "flip_type", "angles")
+
+    def __init__(self, label=(), index=(), loc_noise=None, rot_noise=None, flip_type=None, angles=()):
+        k = len(label)
+        self.label, self.index = [int(v) for v in label], [int(v) for v in index]
+        self.loc_noise = [None] * k if loc_noise is None else list(loc_noise)
+        self.rot_noise = [None] * k if rot_noise is None else list(rot_noise)
+        self.flip_type = [None] * k if flip_type is None else list(flip_type)
+        self.angles = list(angles)
+
+    def __len__(self):
+        return len(self.label)
+
+
+class InstanceAugmentation:
+    """``seg3d.datasets.transforms.instance_augmentation.InstanceAugmentation``: the reference's constructor (a path to
+    the pickled bank, or an ``InstanceBank``) and ``__call__`` signature.  The result points are float64 [n + n_added, D]
+    (the reference's dtype whenever it pastes): the frame's rows unchanged, then the accepted instances.  Where the
+    reference raises, this is defined: without a ground point nothing is placed, without an object point nothing
+    occludes; ``random_rotate=False`` (a branch that reads an unset variable there, :90) is refused."""
+
+    def __init__(self, instance_path, instance_label_ids=[3, 4, 10], ground_label_ids=[17, 18, 19, 20, 21], add_count=5,
+                 random_rotate=True, local_transformation=True, random_flip=True):
+        if not random_rotate:
+            raise Seg3dError("random_rotate=False is not supported: that branch of the reference cannot run")
+        self.bank = instance_path if isinstance(instance_path, InstanceBank) else InstanceBank.from_pickle(instance_path)
+        self.instance_label_ids = list(instance_label_ids)
+        self.ground_label_ids = list(ground_label_ids)
+        self.add_count = int(add_count)
+        self.random_rotate = True
+        self.local_transformation = bool(local_transformation)
+        self.random_flip = bool(random_flip)
+        self.last_decisions = None
+        self.last_bank_rows = None
+
+    def draw(self, rng_state=np.random):
+        """instance_augmentation.py:26-30, then per instance :169, :171, :66, :77, whether or not it is placed."""
+        d = InstanceDraw()
+        label_choice = rng_state.choice(self.instance_label_ids, self.add_count, replace=True)
+        uni_label, uni_count = np.unique(label_choice, return_counts=True)
+        for label_id, count in zip(uni_label, uni_count):
+            if int(label_id) not in self.bank.entries or not self.bank.entries[int(label_id)]:
+                raise Seg3dError(f"the instance bank has no cluster of label {int(label_id)}")
+            for idx in rng_state.choice(len(self.bank.entries[int(label_id)]), count):
+                d.label.append(int(label_id))
+                d.index.append(int(idx))
+                loc = rot = flip = None
+                if self.local_transformation:
+                    loc = rng_state.normal(scale=0.25, size=(1, 3))[0]
+                    rot = rng_state.uniform(-np.pi / 20, np.pi / 20)
+                if self.random_flip:
+                    flip = int(rng_state.choice(5, 1)[0])
+                d.loc_noise.append(loc)
+                d.rot_noise.append(rot)
+                d.flip_type.append(flip)
+                d.angles.append(rng_state.random(20) * np.pi * 2)
+        return d
+
+    def plans(self, draw):
+        out = []
+        for i in range(len(draw)):
+            entries = self.bank.entries.get(draw.label[i], [])
+            if not 0 <= draw.index[i] < len(entries):
+                raise Seg3dError(f"no cluster {draw.index[i]} of label {draw.label[i]} in the instance bank")
+            begin, rows, height = entries[draw.index[i]]
+            out.append(ops.aug_instance_plan(begin, rows, draw.label[i], height, draw.loc_noise[i], draw.rot_noise[i],
+                                             draw.flip_type[i] == 3, draw.angles[i]))
+        return out
+
+    def __call__(self, points, point_image_features, labels, draw=None):
+        be = _backend(points)
+        if points.ndim != 2 or self.bank.dim is None or points.shape[1] != self.bank.dim:
+            raise Seg3dError(f"the instance bank has {self.bank.dim} columns, the frame {tuple(points.shape)}")
+        draw = self.draw() if draw is None else draw
+        plans = self.plans(draw)
+        if be is _Host:
+            add_p, add_l, decisions = ops.aug_instance_paste_host(points, labels, self.ground_label_ids, self.bank.rows, plans)
+            cat, f64 = np.concatenate, (lambda a: np.asarray(a, dtype=np.float64))
+            zeros = lambda m, like: np.zeros((m,) + tuple(like.shape[1:]), dtype=like.dtype)  # noqa: E731
+        else:
+            add_p, add_l, decisions = ops.aug_instance_paste(points, labels, self.ground_label_ids,
+                                                             self.bank.rows_on(points.device), plans)
+            cat, f64 = torch.cat, (lambda a: a.to(torch.float64))
+            zeros = lambda m, like: torch.zeros((m,) + tuple(like.shape[1:]), dtype=like.dtype, device=like.device)  # noqa: E731
+        self.last_decisions = decisions
+        rows = [np.arange(p.row_begin, p.row_begin + p.n_rows) for p, c in zip(plans, decisions) if c >= 0]
+        self.last_bank_rows = np.concatenate(rows + [np.zeros(0, np.int64)]).astype(np.int64)
+        points = cat((f64(points), add_p))
+        labels = cat((labels, add_l))
+        if point_image_features is not None:  # :95-102: pasted rows have no image features
+            m = int(add_p.shape[0])
+            return points, cat((point_image_features, zeros(m, point_image_features))), labels
+        return points, labels
+
+
 class TrainAugmentation:
     """The training pipeline of WaymoDataset (waymo_dataset.py:44-50 after :307-323) on one frame."""
 
-    def __init__(self, rot_range, scale_range, translate_std, sample_ratio, sample_range, polar_mix=None, rng="device"):
+    def __init__(self, rot_range, scale_range, translate_std, sample_ratio, sample_range, polar_mix=None, rng="device",
+                 instance_bank=None):
         if rng not in ("device", "numpy"):
             raise ValueError("rng is 'device' or 'numpy'")
         self.rot_range = [float(v) for v in rot_range]
@@ -118,18 +271,23 @@ class TrainAugmentation:
         self.polar_mix = polar_mix
         self.rng = rng
         self.dim_point = None
+        if instance_bank is not None and not isinstance(instance_bank, InstanceAugmentation):
+            instance_bank = InstanceAugmentation(instance_bank)  # an InstanceBank or a path, the reference's defaults
+        self.instance_aug = instance_bank
 
     @classmethod
-    def from_config(cls, cfg, rng="device", rng_state=np.random):
+    def from_config(cls, cfg, rng="device", rng_state=np.random, instance_bank=None):
         """DATASET.AUG_* of a config.  PolarMix is built as waymo_dataset.py:37-39 builds it (two ``random()`` draws for
-        the paste angles) unless DATASET.USE_MULTI_SWEEPS is set (:307); DIM_POINT columns of a frame are used (:295)."""
+        the paste angles) unless DATASET.USE_MULTI_SWEEPS is set (:307); DIM_POINT columns of a frame are used (:295).
+        ``instance_bank``: an ``InstanceAugmentation`` (or an ``InstanceBank`` / a path for one with the reference's
+        defaults, :41-42); its constructor draws nothing."""
         d = cfg.DATASET
         pm = None
         if not d.USE_MULTI_SWEEPS:
             pm = PolarMix(instance_classes=list(range(13)),
                           rot_angle_range=[rng_state.random() * np.pi * 2 / 3, (rng_state.random() + 1) * np.pi * 2 / 3])
         aug = cls(d.AUG_ROT_RANGE, d.AUG_SCALE_RANGE, d.AUG_TRANSLATE_STD, d.AUG_SAMPLE_RATIO, d.AUG_SAMPLE_RANGE,
-                  polar_mix=pm, rng=rng)
+                  polar_mix=pm, rng=rng, instance_bank=instance_bank)
         aug.dim_point = int(d.DIM_POINT)
         return aug
 
@@ -189,7 +347,10 @@ class TrainAugmentation:
         float32 [n_out, D] ([n_out, 1 + D] with ``batch_id``), ``point_labels``, ``point_image_features`` (None without
         features) and ``cur_point_indices`` (None for single-sweep frames), ready for ``batch.batch_from_resident``; the
         cylinder conversion stays where it is, after augmentation.  Also returned: ``draw`` (the ``AugDraw`` used) and
-        ``source_rows`` (the row of [frame; frame2] behind every output row)."""
+        ``source_rows`` (the row of [frame; frame2] behind every output row).  With an instance bank (and PolarMix
+        running) ``InstanceAugmentation`` pastes into frame 1 first (waymo_dataset.py:313-315, :321), its draws before
+        PolarMix's: ``instance_draw`` is the ``InstanceDraw`` used (replayed from ``params.instance_draw`` when that is
+        set) and a pasted row's ``source_rows`` entry is ``-1 - bank_row``."""
         be = _backend(frame)
         if self.dim_point is not None and frame.shape[1] > self.dim_point:
             frame = frame[:, :self.dim_point]
@@ -200,6 +361,19 @@ class TrainAugmentation:
         multi = cur_point_indices is not None
         mix = self.polar_mix is not None and frame2 is not None and not multi
         n0 = int(frame.shape[0])
+
+        # stage 0: instance copy-paste into frame 1 (one host read of its counts)
+        inst_draw = None
+        n_added = 0
+        if mix and self.instance_aug is not None:
+            inst_draw = params.instance_draw if params is not None and params.instance_draw is not None else \
+                self.instance_aug.draw(rs)
+            res = self.instance_aug(frame, image_features, labels, draw=inst_draw)
+            frame, labels = res[0], res[-1]
+            image_features = res[1] if image_features is not None else None
+            if frame2.dtype != frame.dtype:  # the pasted frame is float64; both frames go through one kernel
+                frame2 = frame2.astype(np.float64) if be is _Host else frame2.to(torch.float64)
+            n_added = int(frame.shape[0]) - n0
 
         # stage 1: the PolarMix row map (one host read of its counts)
         src = op = None
@@ -247,5 +421,13 @@ class TrainAugmentation:
         out["point_labels"] = be.gather(labels, lab2, lab_idx)
         if image_features is not None and (not mix or image_features2 is not None):
             out["point_image_features"] = be.gather(image_features, feat2, lab_idx)
-        out["draw"], out["source_rows"] = d, src2
+        if n_added:  # rows of the pasted frame-1 -> rows of [frame; frame2] as the caller passed them
+            bank_rows = be.index(-1 - self.instance_aug.last_bank_rows, frame)
+            xp = np if be is _Host else torch
+            pasted = (src2 >= n0) & (src2 < n0 + n_added)
+            clamped = xp.where(pasted, src2 - n0, xp.zeros_like(src2))
+            src2 = xp.where(pasted, bank_rows[clamped.astype(np.int64) if be is _Host else clamped.long()],
+                            xp.where(src2 >= n0 + n_added, src2 - n_added, src2))
+        d.instance_draw = inst_draw
+        out["draw"], out["source_rows"], out["instance_draw"] = d, src2, inst_draw
         return out

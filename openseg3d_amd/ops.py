@@ -2727,3 +2727,87 @@ def aug_gather_host(a, b, idx):
     _lib.call("seg3d_aug_gather_host", _hp(a), int(a.shape[0]), _hp(b), 0 if b is None else int(b.shape[0]), row_bytes,
               _hp(idx), m, _hp(out))
     return out
+
+
+# ------------------------------------------------------------------------------------------ instance copy-paste (csrc/augment_instance.hip)
+AUG_MAX_ANGLES = 20
+
+
+class AugInstancePlan(ctypes.Structure):
+    """seg3d_aug_instance_plan (include/seg3d_hip.h): one instance to paste and every number drawn for it."""
+    _fields_ = [("row_begin", ctypes.c_int64), ("n_rows", ctypes.c_int32), ("label", ctypes.c_int32),
+                ("height", ctypes.c_double), ("loc_noise", ctypes.c_double * 3), ("rot_cos", ctypes.c_double),
+                ("rot_sin", ctypes.c_double), ("local_on", ctypes.c_int32), ("flip", ctypes.c_int32),
+                ("n_angles", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ang_cos", ctypes.c_double * AUG_MAX_ANGLES),
+                ("ang_sin", ctypes.c_double * AUG_MAX_ANGLES)]
+
+
+def aug_instance_plan(row_begin, n_rows, label, height, loc_noise=None, rot_noise=None, flip=False, angles=()):
+    """One plan.  loc_noise / rot_noise None: no local transform; the angles' np.cos / np.sin are taken here in float64,
+    as instance_augmentation.py:162-163 takes them."""
+    if len(angles) > AUG_MAX_ANGLES:
+        raise _lib.Seg3dError(f"{len(angles)} candidate angles: the kernels take at most {AUG_MAX_ANGLES}")
+    p = AugInstancePlan()
+    p.row_begin, p.n_rows, p.label, p.height = int(row_begin), int(n_rows), int(label), float(height)
+    p.local_on = int(loc_noise is not None)
+    if loc_noise is not None:
+        for j in range(3):
+            p.loc_noise[j] = float(loc_noise[j])
+        p.rot_cos, p.rot_sin = float(np.cos(rot_noise)), float(np.sin(rot_noise))
+    p.flip = int(bool(flip))
+    p.n_angles = len(angles)
+    for j, a in enumerate(angles):
+        p.ang_cos[j], p.ang_sin[j] = float(np.cos(a)), float(np.sin(a))
+    return p
+
+
+def _aug_instance_args(points, labels, ground_ids, bank, plans, cap_add, host):
+    p, _, n, _, d, pb = _aug_frames(points, None, host)
+    lab, lb = _aug_labels(labels if not host else np.asarray(labels), host)
+    if (lab.size if host else lab.numel()) != n:
+        raise _lib.Seg3dError(f"{lab.shape[0]} labels for {n} points")
+    gids = [int(g) for g in ground_ids]
+    if any(g < 0 or g > 255 for g in gids):
+        raise _lib.Seg3dError("ground_ids must be labels in 0 .. 255")
+    f64 = np.float64 if host else torch.float64
+    if bank.ndim != 2 or bank.dtype != f64 or bank.shape[1] != d:
+        raise _lib.Seg3dError(f"the bank must be float64 [rows, {d}]: the frame's column count")
+    k = len(plans)
+    arr = (AugInstancePlan * max(k, 1))(*plans)
+    need = sum(int(pl.n_rows) for pl in plans)
+    cap = need if cap_add is None else int(cap_add)
+    return p, n, d, pb, lab, lb, (ctypes.c_uint8 * max(len(gids), 1))(*gids), len(gids), arr, k, cap
+
+
+def aug_instance_paste(points, labels, ground_ids, bank, plans, cap_add=None):
+    """seg3d_aug_instance_paste on CUDA tensors: points [n, D] float32 / float64, labels [n] uint8 / int64, bank float64
+    [rows, D] on the same device, plans a list of ``aug_instance_plan``.  Returns (add_points float64 [n_added, D],
+    add_labels [n_added], decisions: list of k accepted candidate indices or -1).  2 k + 1 launches, then ONE host
+    sync: counts and decisions share a buffer and are read together."""
+    _need_gpu(points, labels, bank)
+    p, n, d, pb, lab, lb, gids, ng, arr, k, cap = _aug_instance_args(points, labels, ground_ids, bank, plans, cap_add, False)
+    bank = bank.contiguous()
+    dev = p.device
+    add_points = torch.empty((max(cap, 0), d), dtype=torch.float64, device=dev)
+    add_labels = torch.empty((max(cap, 0),), dtype=lab.dtype, device=dev)
+    info = torch.empty((4 + k,), dtype=torch.int32, device=dev)  # counts [4], then decisions [k]
+    mx = max([int(pl.n_rows) for pl in plans] + [0])
+    ws = _workspace(_lib.query("seg3d_aug_instance_workspace_bytes", n, mx, k), dev)
+    _lib.call("seg3d_aug_instance_paste", _ptr(p), n, d, pb, _ptr(lab), lb, gids, ng, _ptr(bank), int(bank.shape[0]), arr, k,
+              cap, _ptr(add_points), _ptr(add_labels), ctypes.c_void_p(info.data_ptr() + 16), _ptr(info), _ptr(ws),
+              ws.numel(), _stream())
+    host = info.tolist()
+    return add_points[:host[0]], add_labels[:host[0]], host[4:]
+
+
+def aug_instance_paste_host(points, labels, ground_ids, bank, plans, cap_add=None):
+    """seg3d_aug_instance_paste_host: the same from numpy arrays, the same bits; no HIP call."""
+    bank = np.ascontiguousarray(bank)
+    p, n, d, pb, lab, lb, gids, ng, arr, k, cap = _aug_instance_args(points, labels, ground_ids, bank, plans, cap_add, True)
+    add_points = np.empty((max(cap, 0), d), dtype=np.float64)
+    add_labels = np.empty((max(cap, 0),), dtype=lab.dtype)
+    decisions = np.full((max(k, 1),), -1, dtype=np.int32)
+    counts = np.zeros((4,), dtype=np.int32)
+    _lib.call("seg3d_aug_instance_paste_host", _hp(p), n, d, pb, _hp(lab), lb, gids, ng, _hp(bank), int(bank.shape[0]), arr,
+              k, cap, _hp(add_points), _hp(add_labels), _hp(decisions), _hp(counts))
+    return add_points[:counts[0]], add_labels[:counts[0]], decisions[:k].tolist()
