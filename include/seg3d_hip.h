@@ -927,6 +927,67 @@ int seg3d_aug_instance_paste_host(const void* points, int64_t n, int32_t dim, in
                                   int64_t bank_rows, const seg3d_aug_instance_plan* plans, int32_t k, int64_t cap_add,
                                   double* add_points, void* add_labels, int32_t* decisions, int32_t* counts);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame assembly (csrc/frame.hip): what WaymoDataset does on the host between np.load and the voxelizer, and what the
+ * test path does after the head.
+ *
+ * seg3d_frame_assemble -- load_points (seg3d/datasets/waymo_dataset.py:145-154) and load_points_from_sweeps (:156-202)
+ * for ALL sweeps of one frame in one launch.  `table` is a HOST pointer; the kernel receives it by value.  Sweep s holds
+ * n_rows raw rows of `stride` elements (stride >= dim: a raw [N, 15] file or its [:, :dim] copy) of float32
+ * (point_bytes 4) or float64 (8), a row-major 3 x 4 double matrix [R | t], a double time lag and a transform flag.
+ * Output rows [sum_{<s} n, sum_{<=s} n) belong to sweep s, in order; a sweep of 0 rows is legal.  Per row, T the rows'
+ * dtype, in the reference's order:
+ *   col 3 = T(lag)                      (:151, :160 zero the range column, :198 stores ts - sweep_ts; current sweep: 0)
+ *   col 4 = tanh(col 4) evaluated in T  (:153)
+ *   transform = 1:  x' = T((double(x) * m00 + double(y) * m01) + double(z) * m02);  x' = T(double(x') + m03);  likewise
+ *                   y, z with rows 1, 2 of the matrix (:196-197: numpy stores the product, then adds)
+ *   transform = 0:  x, y, z copied bit for bit (the reference never multiplies the current sweep by an identity)
+ *   cols 5 .. dim-1 copied.
+ * Outputs, any subset (NULL = not wanted): out_rows [sum n, dim] in T; out_f32 [sum n, dim] = float(value), round to
+ * nearest (load_data_to_gpu's .float(), data_utils.py:6-15); out_collated [sum n, 1 + dim] float32 with batch_id in
+ * column 0 (collate_batch, waymo_dataset.py:347-352).  1 <= n_sweeps <= 8, 5 <= dim <= 16, sum n <= INT32_MAX:
+ * SEG3D_EINVAL otherwise.  inv(T_cur) @ T_sweep (:193) stays with the caller.
+ * seg3d_frame_assemble_host: the same contract on HOST pointers, plain C++ without a HIP call; every column but col 4
+ * (two tanh libraries) is bit-identical to the device entry.
+ */
+#define SEG3D_FRAME_MAX_SWEEPS 8
+typedef struct {
+  const void* rows;
+  int64_t n_rows;
+  int64_t stride;    /* elements between two rows */
+  double matrix[12]; /* row-major [R | t], 3 x 4 */
+  double lag;
+  int32_t transform; /* 0 / 1 */
+  int32_t reserved;
+} seg3d_sweep;
+typedef struct {
+  int32_t n_sweeps;
+  int32_t reserved;
+  seg3d_sweep sweeps[SEG3D_FRAME_MAX_SWEEPS];
+} seg3d_sweep_table;
+int seg3d_frame_assemble(const seg3d_sweep_table* table, int32_t dim, int32_t point_bytes, void* out_rows,
+                         float* out_f32, float* out_collated, float batch_id, void* stream);
+int seg3d_frame_assemble_host(const seg3d_sweep_table* table, int32_t dim, int32_t point_bytes, void* out_rows,
+                              float* out_f32, float* out_collated, float batch_id);
+
+/* seg3d_range_image_labels -- construct_seg_frame's loop (seg3d/utils/submission.py:27-41).  pred [n] uint8
+ * (pred_bytes 1) or int64 (8); points_ri int32 [n, 3] as (col, row, return index); image1 / image2 int32
+ * [rows, cols, 2], both written in full: channel 0 = 0; channel 1 of image1 at [row, col] = pred + 1 for return index 0,
+ * of image2 for return index 1, 0 where no point lands.  Any other return index is skipped (the parser writes -1 for
+ * the side lidars).  Several points on one pixel: the HIGHEST point index wins (the reference's loop lets the last
+ * point win) -- an integer atomic max of (index + 1) << 8 | (pred + 1), then an unpack pass; independent of the launch
+ * geometry.  A point with return index 0 / 1 whose row / col is outside the image, or whose pred is outside
+ * [0, n_classes), is not written and counted in n_outside (int32 [1], device memory for the device entry; the reference
+ * raises IndexError there).  1 <= n_classes <= 254 so that pred + 1 fits the packing.  workspace: 16 B per pixel.
+ * The *_host twin: host pointers, no HIP call, the same integers.
+ */
+size_t seg3d_range_image_workspace_bytes(int32_t rows, int32_t cols);
+int seg3d_range_image_labels(const void* pred, int32_t pred_bytes, const int32_t* points_ri, int64_t n, int32_t rows,
+                             int32_t cols, int32_t n_classes, int32_t* image1, int32_t* image2, int32_t* n_outside,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int seg3d_range_image_labels_host(const void* pred, int32_t pred_bytes, const int32_t* points_ri, int64_t n, int32_t rows,
+                                  int32_t cols, int32_t n_classes, int32_t* image1, int32_t* image2, int32_t* n_outside);
+
 #ifdef __cplusplus
 }
 #endif

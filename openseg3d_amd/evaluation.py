@@ -247,6 +247,28 @@ def segment_frame(model, data_dict, augmentor=None, metric=None, views_per_forwa
     return ops.argmax_confusion(scores.float(), labels=labels, hist=hist, n_views=n_views)
 
 
+def segment_test_frame(model, batch, augmentor=None, n_classes=None, views_per_forward=None):
+    """``semseg_for_one_frame`` of tools/test.py:37-61 without the protobuf: the frame's predicted labels (argmax of the
+    logits, or of ``MultiScaleFlipAug``'s mean probability for single-sweep configs) written into the two range images of
+    the top lidar on the device (seg3d_range_image_labels; submission.py:27-41).  ``batch``: one frame with ``points_ri``
+    and ``filename``, as ``WaymoDataset(mode='testing')`` delivers it.  Returns ``context_name``,
+    ``frame_timestamp_micros`` and the int32 [64, 2650, 2] numpy images ``ri_return1`` / ``ri_return2``; packing them
+    into Waymo's SegmentationFrame proto needs ``waymo_open_dataset`` and is left to the caller."""
+    if int(batch.get("batch_size", 1)) != 1:
+        raise ValueError("segment_test_frame takes one frame (tools/test.py reads filename[0])")
+    ri = batch["points_ri"]
+    name = batch["filename"][0] if isinstance(batch["filename"], (list, tuple)) else batch["filename"]
+    pred = segment_frame(model, {k: v for k, v in batch.items() if k not in ("points_ri", "point_labels")}, augmentor,
+                         views_per_forward=views_per_forward)
+    if not torch.is_tensor(ri):
+        ri = torch.from_numpy(np.ascontiguousarray(ri, dtype=np.int32))
+    ri = ri.to(device=pred.device, dtype=torch.int32)
+    img1, img2 = ops.range_image_labels(pred, ri, 254 if n_classes is None else int(n_classes))
+    context_name, timestamp = name.split('-')[:2]
+    return {"context_name": context_name, "frame_timestamp_micros": int(timestamp),
+            "ri_return1": img1.cpu().numpy(), "ri_return2": img2.cpu().numpy()}
+
+
 def evaluate(model, frames, class_names, augmentor=None, views_per_forward=None):
     """tools/eval.py:35-64: every frame through segment_frame, scored by IOUMetric; returns get_metric()."""
     model.eval()

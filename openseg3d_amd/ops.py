@@ -2811,3 +2811,155 @@ def aug_instance_paste_host(points, labels, ground_ids, bank, plans, cap_add=Non
     _lib.call("seg3d_aug_instance_paste_host", _hp(p), n, d, pb, _hp(lab), lb, gids, ng, _hp(bank), int(bank.shape[0]), arr,
               k, cap, _hp(add_points), _hp(add_labels), _hp(decisions), _hp(counts))
     return add_points[:counts[0]], add_labels[:counts[0]], decisions[:k].tolist()
+
+
+# ------------------------------------------------------------------------------------------ frame assembly (csrc/frame.hip)
+FRAME_MAX_SWEEPS = 8
+
+
+class Sweep(ctypes.Structure):
+    """seg3d_sweep (include/seg3d_hip.h)."""
+    _fields_ = [("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int64), ("stride", ctypes.c_int64),
+                ("matrix", ctypes.c_double * 12), ("lag", ctypes.c_double), ("transform", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class SweepTable(ctypes.Structure):
+    """seg3d_sweep_table: up to 8 sweeps of one frame; ``arrays`` keeps the rows alive, ``dim`` / ``dtype`` describe them."""
+    _fields_ = [("n_sweeps", ctypes.c_int32), ("reserved", ctypes.c_int32), ("sweeps", Sweep * FRAME_MAX_SWEEPS)]
+
+
+def sweep_table(sweeps, matrices=None, lags=None, dim=None):
+    """The sweeps of one frame, current sweep first (waymo_dataset.py:156-202).  sweeps: 2-d float32 / float64 numpy
+    arrays (host entry) or CUDA tensors (device entry) of one dtype, unit stride along a row; a ``[:, :dim]`` view of a
+    raw ``[N, 15]`` array is taken as it is, through its row stride.  matrices[s]: None (x, y, z copied bit for bit: the
+    current sweep) or the 4 x 4 / 3 x 4 float64 ``inv(T_cur) @ T_sweep``, which stays a numpy product on the host as at
+    :193; lags[s]: ``ts - sweep_ts`` (0 for the current sweep).  dim: the columns used (default: the arrays' width).
+    More than 8 sweeps are recorded in ``n_sweeps`` and refused by the library."""
+    sweeps = list(sweeps)
+    matrices = [None] * len(sweeps) if matrices is None else list(matrices)
+    lags = [0.0] * len(sweeps) if lags is None else list(lags)
+    if not sweeps or len(matrices) != len(sweeps) or len(lags) != len(sweeps):
+        raise _lib.Seg3dError("sweep_table: one matrix (or None) and one lag per sweep, at least one sweep")
+    host = isinstance(sweeps[0], np.ndarray)
+    t = SweepTable()
+    t.n_sweeps = len(sweeps)
+    t.arrays, t.host = sweeps, host
+    t.dtype = sweeps[0].dtype
+    t.dim = int(sweeps[0].shape[1] if dim is None else dim)
+    f32, f64 = (np.float32, np.float64) if host else (torch.float32, torch.float64)
+    for s, a in enumerate(sweeps):
+        if isinstance(a, np.ndarray) != host or (not host and not (isinstance(a, torch.Tensor) and a.is_cuda)):
+            raise _lib.Seg3dError("sweep_table: all sweeps numpy arrays (host entry) or all CUDA tensors (device entry)")
+        if a.ndim != 2 or a.dtype != t.dtype or a.dtype not in (f32, f64) or a.shape[1] < t.dim:
+            raise _lib.Seg3dError("sweep_table: sweeps are [N, >= dim] arrays of one float dtype")
+        item = a.itemsize if host else a.element_size()
+        row_stride, col_stride = (a.strides[0] // item, a.strides[1] // item) if host else (a.stride(0), a.stride(1))
+        if a.shape[0] > 0 and (col_stride != 1 or (a.shape[0] > 1 and row_stride < t.dim)):
+            raise _lib.Seg3dError("sweep_table: rows must have unit column stride (pass a row slice or a [:, :dim] view)")
+        if s >= FRAME_MAX_SWEEPS:
+            continue
+        e = t.sweeps[s]
+        e.rows = (a.ctypes.data if host else a.data_ptr()) if a.shape[0] else None
+        e.n_rows, e.stride = int(a.shape[0]), int(row_stride if a.shape[0] > 1 else t.dim)
+        e.lag = float(lags[s])
+        if matrices[s] is not None:
+            m = np.asarray(matrices[s], dtype=np.float64)
+            if m.shape not in ((4, 4), (3, 4)):
+                raise _lib.Seg3dError("sweep_table: a sweep's matrix is 4 x 4 or 3 x 4")
+            e.transform = 1
+            for j, v in enumerate(m[:3].reshape(-1)):
+                e.matrix[j] = float(v)
+    return t
+
+
+def _frame_outputs(table, want, empty):
+    n = sum(int(a.shape[0]) for a in table.arrays)
+    unknown = set(want) - {"rows", "f32", "collated"}
+    if unknown or not want:
+        raise _lib.Seg3dError("frame_assemble: want is a non-empty subset of ('rows', 'f32', 'collated')")
+    f32 = np.float32 if table.host else torch.float32
+    return n, {"rows": empty((n, table.dim), table.dtype) if "rows" in want else None,
+               "f32": empty((n, table.dim), f32) if "f32" in want else None,
+               "collated": empty((n, table.dim + 1), f32) if "collated" in want else None}
+
+
+def frame_assemble(table, want=("collated",), batch_id=0):
+    """seg3d_frame_assemble: all sweeps of one frame -> its rows, one launch.  ``table`` from ``sweep_table`` over CUDA
+    tensors.  want: any of 'rows' ([sum N, dim] in the rows' own dtype), 'f32' (float32 [sum N, dim]) and 'collated'
+    (float32 [sum N, 1 + dim], batch_id in column 0).  Returns a dict of the wanted tensors."""
+    if table.host:
+        raise _lib.Seg3dError("frame_assemble takes a table of CUDA tensors (frame_assemble_host takes numpy arrays)")
+    dev = table.arrays[0].device
+    _, out = _frame_outputs(table, want, lambda shape, dt: torch.empty(shape, dtype=dt, device=dev))
+    _lib.call("seg3d_frame_assemble", ctypes.byref(table), table.dim, 4 if table.dtype == torch.float32 else 8,
+              _ptr(out["rows"]), _ptr(out["f32"]), _ptr(out["collated"]), float(batch_id), _stream())
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def frame_assemble_host(table, want=("rows",), batch_id=0):
+    """seg3d_frame_assemble_host: the same on numpy arrays; plain C++ of the same library, no HIP call."""
+    if not table.host:
+        raise _lib.Seg3dError("frame_assemble_host takes a table of numpy arrays")
+    _, out = _frame_outputs(table, want, lambda shape, dt: np.empty(shape, dtype=dt))
+    _lib.call("seg3d_frame_assemble_host", ctypes.byref(table), table.dim, 4 if table.dtype == np.float32 else 8,
+              _hp(out["rows"]), _hp(out["f32"]), _hp(out["collated"]), float(batch_id))
+    return {k: v for k, v in out.items() if v is not None}
+
+
+RANGE_IMAGE_SHAPE = (64, 2650)  # the top lidar's range image (submission.py:29-30)
+
+
+class RangeImageIndexError(IndexError, _lib.Seg3dError):
+    """A point's (row, col) lies outside the range image, or its label outside [0, n_classes)."""
+
+
+def range_image_labels(pred, points_ri, n_classes, rows=RANGE_IMAGE_SHAPE[0], cols=RANGE_IMAGE_SHAPE[1], check=True):
+    """seg3d_range_image_labels (submission.py:27-41): pred uint8 / int64 [N] and points_ri int32 [N, 3] CUDA tensors ->
+    two int32 [rows, cols, 2] images; channel 1 = pred + 1 at the pixels of return 0 / return 1, the highest point index
+    winning a shared pixel.  check: read the out-of-image count back (one host sync) and raise where the reference
+    raises IndexError; check=False returns (image1, image2, count tensor)."""
+    _need_gpu(pred, points_ri)
+    if n_classes > 254:
+        raise _lib.Seg3dError(f"{n_classes} classes: label + 1 must fit 8 bits (at most 254)")
+    if pred.dtype not in (torch.uint8, torch.int64) or pred.dim() != 1:
+        raise _lib.Seg3dError("pred must be a uint8 or int64 [N] tensor")
+    if points_ri.dtype != torch.int32 or points_ri.dim() != 2 or points_ri.shape[1] != 3 or points_ri.shape[0] != pred.shape[0]:
+        raise _lib.Seg3dError("points_ri must be an int32 [N, 3] tensor of (col, row, return index)")
+    pred, points_ri = pred.contiguous(), points_ri.contiguous()
+    dev = pred.device
+    img1 = torch.empty((rows, cols, 2), dtype=torch.int32, device=dev)
+    img2 = torch.empty((rows, cols, 2), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws = _workspace(_lib.query("seg3d_range_image_workspace_bytes", int(rows), int(cols)), dev)
+    _lib.call("seg3d_range_image_labels", _ptr(pred), 1 if pred.dtype == torch.uint8 else 8, _ptr(points_ri),
+              int(pred.shape[0]), int(rows), int(cols), int(n_classes), _ptr(img1), _ptr(img2), _ptr(count), _ptr(ws),
+              ws.numel(), _stream())
+    if not check:
+        return img1, img2, count
+    bad = int(count.item())
+    if bad:
+        raise RangeImageIndexError(f"{bad} points lie outside the {rows} x {cols} range image or carry a label outside "
+                                   f"[0, {n_classes})")
+    return img1, img2
+
+
+def range_image_labels_host(pred, points_ri, n_classes, rows=RANGE_IMAGE_SHAPE[0], cols=RANGE_IMAGE_SHAPE[1]):
+    """seg3d_range_image_labels_host: the same on numpy arrays (no HIP call); raises on an out-of-image point."""
+    if n_classes > 254:
+        raise _lib.Seg3dError(f"{n_classes} classes: label + 1 must fit 8 bits (at most 254)")
+    pred = np.ascontiguousarray(pred)
+    ri = np.ascontiguousarray(points_ri)
+    if pred.dtype not in (np.uint8, np.int64) or pred.ndim != 1:
+        raise _lib.Seg3dError("pred must be a uint8 or int64 [N] array")
+    if ri.dtype != np.int32 or ri.ndim != 2 or ri.shape[1] != 3 or ri.shape[0] != pred.shape[0]:
+        raise _lib.Seg3dError("points_ri must be an int32 [N, 3] array of (col, row, return index)")
+    img1 = np.empty((rows, cols, 2), dtype=np.int32)
+    img2 = np.empty((rows, cols, 2), dtype=np.int32)
+    count = np.zeros((1,), dtype=np.int32)
+    _lib.call("seg3d_range_image_labels_host", _hp(pred), 1 if pred.dtype == np.uint8 else 8, _hp(ri), int(pred.shape[0]),
+              int(rows), int(cols), int(n_classes), _hp(img1), _hp(img2), _hp(count))
+    if int(count[0]):
+        raise RangeImageIndexError(f"{int(count[0])} points lie outside the {rows} x {cols} range image or carry a label "
+                                   f"outside [0, {n_classes})")
+    return img1, img2
