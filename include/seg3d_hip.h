@@ -928,6 +928,65 @@ int seg3d_aug_instance_paste_host(const void* points, int64_t n, int32_t dim, in
                                   double* add_points, void* add_labels, int32_t* decisions, int32_t* counts);
 
 /* ------------------------------------------------------------------------------------------
+ * Instance bank extraction (csrc/instance_extract.hip): the per-frame body of tools/extract_instances.py:46-76 -- DBSCAN
+ * over the xy of each target label's rows, then centre, radius and height above the nearest ground row per cluster --
+ * for ALL target labels of a frame in one call.
+ *
+ * In:  points [n, dim] float32 (point_bytes 4) or float64 (8), converted exactly to double, 3 <= dim <= 16; labels [n]
+ *      uint8 (label_bytes 1) or int64 (8), after load_label (:19-23); target_ids host uint8 [k] (distinct) with
+ *      min_points host int32 [k] >= 1 (TARGET_LABEL_ID / TARGET_MIN_POINT_NUM, :10-11), 1 <= k <= 8; ground_ids host
+ *      uint8 [g], 1 <= g <= 8 (:37); eps > 0 (:56); cap_clusters >= 0; n <= INT32_MAX - 1.  Outside: SEG3D_EINVAL.
+ * DBSCAN, as sklearn's result on `DBSCAN(eps, min_samples).fit(target_points[:, :2])` is defined (not its code): rows i, j
+ *      of one target label are neighbours iff (dx*dx + dy*dy) <= eps*eps in double without fused multiply-add, a row
+ *      being its own neighbour; a row with >= min_points neighbours is core; a cluster is a connected component of core
+ *      rows, clusters of a label numbered by ascending lowest core row; a non-core row with a core neighbour joins the
+ *      LOWEST-NUMBERED cluster among its core neighbours, any other non-core row is noise.  Rows of different labels
+ *      never neighbour each other.  Global cluster ids: by position of the label in target_ids, then that order.
+ * Out: point_cluster int32 [n]: the row's global cluster id, -1 for noise and non-target rows (true ids even beyond
+ *      cap_clusters).  cluster_rows int32 [n]: the clustered rows grouped by cluster, ascending row inside a cluster
+ *      (the row order of `target_points[cluster_ids == c]`, :65), -1 behind the counts[2] used entries.
+ *      clusters [cap_clusters]: per cluster label, begin / rows into cluster_rows, center = mean xyz (:66; partial sum
+ *      t adds the cluster's rows t, t + 256, ..., the 256 partial sums fold by halving, then one division), radius =
+ *      max sqrt((dx*dx + dy*dy) + dz*dz) to the centre (:26-33, :67), kept = 1 iff a ground row has that distance d to
+ *      the centre < 1.2 * radius (:70, strict), height = center z - z of the ground row with the smallest (d, row) (:74-75,
+ *      np.argmin's tie rule), 0 when not kept.  A frame without ground rows keeps nothing (the reference raises, :50).
+ *      counts int32 [4] = {clusters found, clusters kept among the first cap_clusters, clustered rows, target rows}.
+ *      More clusters than cap_clusters: the first cap_clusters entries are complete, counts[0] is the true number and
+ *      nothing is written behind clusters[cap_clusters - 1].
+ * Device: rows are binned on a grid of side eps (one 64-bit key label | floor cell x | floor cell y per row, rocPRIM
+ *      radix sort; the 3 x 3 neighbouring cells of a row are three contiguous key ranges found by bisection), the core
+ *      count, a lock-free union-find over the core rows that always hooks the larger root under the smaller (integer
+ *      compare-and-swap only; every find walks strictly downward, so all loops terminate and the root of a component
+ *      is its lowest core row), the border rule, a second stable sort by (label position, root row) that yields
+ *      cluster_rows and the numbering, one workgroup per cluster for centre and radius, and one sweep over the frame
+ *      for the nearest ground row of eight clusters at a time (wave64 shuffles -> LDS -> one record per workgroup -> a
+ *      fold).  No allocation, no host synchronisation, no float atomics; every reduction is an integer, an exact
+ *      lexicographic minimum or a fixed-order sum, so the result does not depend on the launch geometry or the
+ *      schedule.  counts and every output are device memory; the *_host twin takes host pointers, makes no HIP call
+ *      and returns the same integers and the same double bits.
+ */
+typedef struct {
+  int32_t label; /* the target label id */
+  int32_t begin; /* first entry in cluster_rows */
+  int32_t rows;
+  int32_t kept; /* 0 / 1 */
+  double center[3];
+  double radius;
+  double height;
+} seg3d_instance_cluster;
+size_t seg3d_instance_extract_workspace_bytes(int64_t n, int32_t cap_clusters);
+int seg3d_instance_extract(const void* points, int64_t n, int32_t dim, int32_t point_bytes, const void* labels,
+                           int32_t label_bytes, const uint8_t* target_ids, const int32_t* min_points, int32_t k,
+                           const uint8_t* ground_ids, int32_t g, double eps, int32_t cap_clusters, int32_t* point_cluster,
+                           int32_t* cluster_rows, seg3d_instance_cluster* clusters, int32_t* counts, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int seg3d_instance_extract_host(const void* points, int64_t n, int32_t dim, int32_t point_bytes, const void* labels,
+                                int32_t label_bytes, const uint8_t* target_ids, const int32_t* min_points, int32_t k,
+                                const uint8_t* ground_ids, int32_t g, double eps, int32_t cap_clusters,
+                                int32_t* point_cluster, int32_t* cluster_rows, seg3d_instance_cluster* clusters,
+                                int32_t* counts);
+
+/* ------------------------------------------------------------------------------------------
  * Frame assembly (csrc/frame.hip): what WaymoDataset does on the host between np.load and the voxelizer, and what the
  * test path does after the head.
  *

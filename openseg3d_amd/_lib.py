@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -155,6 +155,11 @@ SIGNATURES = {
                                                 _p, _p, _p, _sz, _p]),
     "seg3d_aug_instance_paste_host": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _p, _i64, _p, _i32, _i64, _p,
                                                      _p, _p, _p]),
+    "seg3d_instance_extract_workspace_bytes": (_sz, [_i64, _i32]),
+    "seg3d_instance_extract": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _d, _i32, _p, _p, _p, _p,
+                                              _p, _sz, _p]),
+    "seg3d_instance_extract_host": (ctypes.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _i32, _d, _i32, _p, _p, _p,
+                                                   _p]),
     "seg3d_frame_assemble": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _p, _f, _p]),
     "seg3d_frame_assemble_host": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _p, _f]),
     "seg3d_range_image_workspace_bytes": (_sz, [_i32, _i32]),

@@ -157,6 +157,66 @@ class InstanceBank:
         return self.to(device)._device_rows[torch.device(device)]
 
 
+class InstanceBankBuilder:
+    """The reference's ``tools/extract_instances.py`` as a class, for all target labels at once (the script is edited and
+    run once per label): ``add`` a training frame after ``load_points`` / ``load_label``, read ``instances``.  Per frame
+    and label, DBSCAN over the xy of the label's rows (``eps``, ``min_points[label]``: the script's TARGET_MIN_POINT_NUM),
+    and every cluster with a ground row within 1.2 radii of its centre becomes ``{'cluster_points': the cluster's raw rows
+    in the frame's dtype and row order, 'cluster_height': float}`` (:56-76) -- in the library
+    (csrc/instance_extract.hip): numpy frames through the host entry, CUDA tensors through the device entry, the same
+    clusters and the same heights bit for bit.  The device path reads back the counts and the cluster table in one copy
+    per frame, then the kept rows in a second one.  Centre, radius and height are computed in double whatever the
+    frame's dtype (numpy's ``np.mean`` of a float32 file runs in float32)."""
+
+    def __init__(self, label_ids=[3, 4, 10], min_points={3: 120, 4: 30, 10: 30}, ground_label_ids=[17, 18, 19, 20, 21],
+                 eps=0.25):
+        self.label_ids = [int(v) for v in label_ids]
+        if isinstance(min_points, dict):
+            missing = [v for v in self.label_ids if v not in min_points]
+            if missing:
+                raise Seg3dError(f"no min_points for labels {missing}")
+            self.min_points = [int(min_points[v]) for v in self.label_ids]
+        else:
+            self.min_points = [int(v) for v in min_points]
+        self.ground_label_ids = [int(v) for v in ground_label_ids]
+        self.eps = float(eps)
+        self.instances = {v: [] for v in self.label_ids}
+        self.frames = 0
+        self.last_counts = None
+
+    def add(self, points, labels):
+        """One frame; returns how many instances it contributed."""
+        be = _backend(points)
+        if be is _Host:
+            _, rows, table, counts = ops.instance_extract_host(points, labels, self.label_ids, self.min_points,
+                                                               self.ground_label_ids, self.eps)
+            points = np.asarray(points)
+        else:
+            _, rows, table, counts = ops.instance_extract(points, labels, self.label_ids, self.min_points,
+                                                          self.ground_label_ids, self.eps)
+        self.frames += 1
+        self.last_counts = counts
+        kept = [c for c in table if c["kept"]]
+        if not kept:
+            return 0
+        if be is _Host:
+            picked = points[rows[:counts[2]]]
+        else:
+            picked = points[rows[:counts[2]].long()].cpu().numpy()
+        for c in kept:
+            self.instances[int(c["label"])].append({"cluster_height": float(c["height"]),
+                                                    "cluster_points": picked[c["begin"]:c["begin"] + c["rows"]].copy()})
+        return len(kept)
+
+    def bank(self):
+        return InstanceBank(self.instances)
+
+    def save(self, path):
+        """The pickle the reference's ``InstanceAugmentation(instance_path)`` loads (instance_augmentation.py:21-23)."""
+        with open(path, "wb") as f:
+            pickle.dump(self.instances, f)
+
+
 class InstanceDraw:
     """Every number ``InstanceAugmentation`` draws for one frame: per instance, in processing order, ``label``,
     ``index`` (into the bank's list of that label), ``loc_noise`` [3] and ``rot_noise`` (None without the local

@@ -2813,6 +2813,76 @@ def aug_instance_paste_host(points, labels, ground_ids, bank, plans, cap_add=Non
     return add_points[:counts[0]], add_labels[:counts[0]], decisions[:k].tolist()
 
 
+# ------------------------------------------------------------------------------------------ instance bank extraction (csrc/instance_extract.hip)
+class InstanceCluster(ctypes.Structure):
+    """seg3d_instance_cluster (include/seg3d_hip.h): 56 bytes, seven 8-byte words."""
+    _fields_ = [("label", ctypes.c_int32), ("begin", ctypes.c_int32), ("rows", ctypes.c_int32), ("kept", ctypes.c_int32),
+                ("center", ctypes.c_double * 3), ("radius", ctypes.c_double), ("height", ctypes.c_double)]
+
+
+INSTANCE_CLUSTER_DTYPE = np.dtype([("label", np.int32), ("begin", np.int32), ("rows", np.int32), ("kept", np.int32),
+                                   ("center", np.float64, (3,)), ("radius", np.float64), ("height", np.float64)])
+INSTANCE_EXTRACT_CAP = 1024  # the wrappers' first guess of cap_clusters; a frame with more is run once more
+
+
+def _instance_extract_args(points, labels, target_ids, min_points, ground_ids, host):
+    p, _, n, _, d, pb = _aug_frames(points, None, host)
+    lab, lb = _aug_labels(labels if not host else np.asarray(labels), host)
+    if (lab.size if host else lab.numel()) != n:
+        raise _lib.Seg3dError(f"{lab.shape[0]} labels for {n} points")
+    tids, gids, mins = [int(t) for t in target_ids], [int(g) for g in ground_ids], [int(m) for m in min_points]
+    if any(v < 0 or v > 255 for v in tids + gids) or len(mins) != len(tids):
+        raise _lib.Seg3dError("target / ground ids must be labels in 0 .. 255, with one min_points per target id")
+    return (p, n, d, pb, lab, lb, (ctypes.c_uint8 * max(len(tids), 1))(*tids), (ctypes.c_int32 * max(len(mins), 1))(*mins),
+            len(tids), (ctypes.c_uint8 * max(len(gids), 1))(*gids), len(gids))
+
+
+def instance_extract(points, labels, target_ids, min_points, ground_ids, eps=0.25, cap_clusters=None):
+    """seg3d_instance_extract on CUDA tensors: points [n, D] float32 / float64, labels [n] uint8 / int64.  Returns
+    (point_cluster int32 [n] and cluster_rows int32 [n] on the device, clusters: a numpy record array
+    (``INSTANCE_CLUSTER_DTYPE``) of min(found, cap) entries, counts: list of 4).  One host sync per call: counts and the
+    cluster table share a buffer and are read together.  cap_clusters None: ``INSTANCE_EXTRACT_CAP``, and a frame with
+    more clusters is run once more with the true number; an explicit cap is used as given."""
+    _need_gpu(points, labels)
+    p, n, d, pb, lab, lb, tids, mins, k, gids, g = _instance_extract_args(points, labels, target_ids, min_points, ground_ids,
+                                                                          False)
+    dev = p.device
+    point_cluster = torch.empty((n,), dtype=torch.int32, device=dev)
+    cluster_rows = torch.empty((n,), dtype=torch.int32, device=dev)
+    cap = INSTANCE_EXTRACT_CAP if cap_clusters is None else int(cap_clusters)
+    while True:
+        info = torch.empty((16 + 56 * max(cap, 0),), dtype=torch.uint8, device=dev)  # counts [4], then the table
+        ws = _workspace(_lib.query("seg3d_instance_extract_workspace_bytes", n, cap), dev)
+        _lib.call("seg3d_instance_extract", _ptr(p), n, d, pb, _ptr(lab), lb, tids, mins, k, gids, g, float(eps), cap,
+                  _ptr(point_cluster), _ptr(cluster_rows), ctypes.c_void_p(info.data_ptr() + 16), _ptr(info), _ptr(ws),
+                  ws.numel(), _stream())
+        raw = info.cpu().numpy()
+        counts = raw[:16].view(np.int32).tolist()
+        if cap_clusters is None and counts[0] > cap:
+            cap = counts[0]
+            continue
+        used = min(counts[0], cap)
+        return point_cluster, cluster_rows, raw[16:16 + 56 * used].view(INSTANCE_CLUSTER_DTYPE).copy(), counts
+
+
+def instance_extract_host(points, labels, target_ids, min_points, ground_ids, eps=0.25, cap_clusters=None):
+    """seg3d_instance_extract_host: the same from numpy arrays, the same integers and double bits; no HIP call."""
+    p, n, d, pb, lab, lb, tids, mins, k, gids, g = _instance_extract_args(points, labels, target_ids, min_points, ground_ids,
+                                                                          True)
+    point_cluster = np.empty((n,), dtype=np.int32)
+    cluster_rows = np.empty((n,), dtype=np.int32)
+    cap = INSTANCE_EXTRACT_CAP if cap_clusters is None else int(cap_clusters)
+    while True:
+        clusters = np.zeros((max(cap, 0),), dtype=INSTANCE_CLUSTER_DTYPE)
+        counts = np.zeros((4,), dtype=np.int32)
+        _lib.call("seg3d_instance_extract_host", _hp(p), n, d, pb, _hp(lab), lb, tids, mins, k, gids, g, float(eps), cap,
+                  _hp(point_cluster), _hp(cluster_rows), _hp(clusters), _hp(counts))
+        if cap_clusters is None and counts[0] > cap:
+            cap = int(counts[0])
+            continue
+        return point_cluster, cluster_rows, clusters[:min(int(counts[0]), cap)].copy(), counts.tolist()
+
+
 # ------------------------------------------------------------------------------------------ frame assembly (csrc/frame.hip)
 FRAME_MAX_SWEEPS = 8
 
