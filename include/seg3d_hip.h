@@ -675,6 +675,49 @@ int seg3d_lovasz_softmax_fwd(const float* logits, const int64_t* labels, int64_t
 int seg3d_lovasz_softmax_bwd(const float* logits, const float* coef, const float* stats, const float* grad_out,
                              int64_t n, int32_t c, float* dlogits, void* stream);
 
+/*
+ * FocalLoss (seg3d/models/losses/focal_loss.py:51-92) on logits [n, c <= 64] with int64 labels, sigmoid focal loss against
+ * the one-hot label.  Valid rows: label != ignore_index; a label outside [0, c) is skipped and not counted either, as in
+ * seg3d_cross_entropy_fwd (the reference's one_hot raises there -- the one deviation).  Per element of a valid row, with
+ * t = [j == label]:  bce = max(x, 0) - x t + log1p(exp(-|x|)),  q = 1 - p_t (sigmoid(-x) for t = 1, sigmoid(x) for t = 0),
+ *   loss = alpha_t * bce * q^gamma * class_weight[j],  alpha_t = alpha t + (1 - alpha)(1 - t), left out when alpha < 0.
+ * gamma >= 0 (0, 1, 2 without powf); class_weight nullable float [c]; reduction SEG3D_REDUCE_SUM or SEG3D_REDUCE_MEAN
+ * (sum / (n_valid * c); 0, not NaN, when no row is valid).  The reference's 'none' has a data-dependent shape and stays
+ * with the caller.
+ * forward : stats [2] = {loss, n_valid}, kept for backward.
+ * backward: recomputes every term from logits (nothing [n, c] is kept); dlogits [n, c] written for every element, exactly
+ *           0 on rows that are not valid.
+ * Deterministic (per-workgroup partials, fixed-order finalize, no floating-point atomics).  seg3d_pointwise_loss_workspace_bytes
+ * serves the focal and the dice forward.
+ */
+size_t seg3d_pointwise_loss_workspace_bytes(int64_t n);
+int seg3d_focal_loss_fwd(const float* logits, const int64_t* labels, int64_t n, int32_t c, int64_t ignore_index, float gamma,
+                         float alpha, const float* class_weight, int32_t reduction, float* stats, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int seg3d_focal_loss_bwd(const float* logits, const int64_t* labels, const float* stats, const float* grad_out, int64_t n,
+                         int32_t c, int64_t ignore_index, float gamma, float alpha, const float* class_weight,
+                         int32_t reduction, float* dlogits, void* stream);
+
+/*
+ * DiceLoss (seg3d/models/losses/dice_loss.py:9-43 dice_loss / binary_dice_loss, :84-114 forward;
+ * seg3d/utils/loss_utils.py:43-73 weight_reduce_loss) on logits [n, c <= 64] with int64 labels.  On [n, c] rows the
+ * reference reduces to, with p = softmax(x_r), t = onehot(clamp(y_r, 0, c - 1)), v_r = [y_r != ignore_index]:
+ *   loss = loss_weight / c * sum_{i != ignore_index} class_weight[i] / n * sum_r (1 - (2 p_ri t_ri v_r + smooth) /
+ *                                                                                  (p_ri^exponent + t_ri^exponent + smooth))
+ * The mean runs over ALL n rows and v masks the numerator only, so rows with the ignore label have a gradient (through
+ * the denominator, with the clamped label's one-hot in it).  avg_factor >= 0: the scalar is divided by avg_factor +
+ * FLT_EPSILON (reduction 'mean' with avg_factor, loss_utils.py:65-69); avg_factor < 0: none.  exponent 1 and 2 run
+ * without powf.  class_weight nullable float [c].  n = 0 gives 0.
+ * forward : loss [1].   backward: recomputes the row softmax, dlogits_rj = p_rj (g_j - sum_i g_i p_ri) with
+ *           g_i = d loss / d p_ri, times grad_out[0].  Deterministic as above.
+ */
+int seg3d_dice_loss_fwd(const float* logits, const int64_t* labels, int64_t n, int32_t c, int64_t ignore_index, float smooth,
+                        float exponent, const float* class_weight, float loss_weight, float avg_factor, float* loss,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int seg3d_dice_loss_bwd(const float* logits, const int64_t* labels, const float* grad_out, int64_t n, int32_t c,
+                        int64_t ignore_index, float smooth, float exponent, const float* class_weight, float loss_weight,
+                        float avg_factor, float* dlogits, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Evaluation path (csrc/eval.hip): tools/eval.py:35-64 with --tta, test_time_aug.py:15-35 (MultiScaleFlipAug),
  * seg3d/core/evaluation/iou_metric.py:21-53 (IOUMetric.fast_hist / add).  None of the three allocates.

@@ -3,16 +3,22 @@
   seg3d/models/builder.py:26-40                          build_criterion: MODEL.LOSSES = {'ohem_ce': 1.0, 'lovasz': 1.0}
   seg3d/models/losses/ohem_cross_entropy_loss.py:5-38    OHEMCrossEntropyLoss
   seg3d/models/losses/lovasz_loss.py:215-290             LovaszLoss
+  seg3d/models/losses/focal_loss.py:6-105                FocalLoss
+  seg3d/models/losses/dice_loss.py:9-43, 46-127          DiceLoss (seg3d/utils/loss_utils.py:9-22, 43-73)
   tools/train.py:71-110                                  compute_loss (point, voxel and 0.4 x auxiliary terms)
 
 Same class names, constructor arguments and ``loss_name`` properties.  The configurations build_criterion can produce
 (OHEM by probability threshold, multi-class Lovasz over the whole batch) run in libseg3d_hip.so: one pass each way for
 the cross-entropy terms, one device sort for all classes of the Lovasz term.  Options the builder never sets (OHEM by
-keep_ratio, per-image / binary Lovasz) are composed from torch ops on the same device tensors.
+keep_ratio, per-image / binary Lovasz) are composed from torch ops on the same device tensors.  FocalLoss and DiceLoss,
+which no configuration of the reference builds but its package exports, run in the library too on CUDA float32 inputs
+(build_criterion keys 'focal' and 'dice', beyond the reference's three); other inputs take a torch composition of the
+same formulas.
 """
 import contextlib
 import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -113,8 +119,133 @@ class LovaszLoss(nn.Module):
         return self._loss_name
 
 
+def get_class_weight(class_weight):
+    """loss_utils.py:9-22: a list is taken as given, a str is the path of an .npy file."""
+    if isinstance(class_weight, str):
+        if not class_weight.endswith(".npy"):
+            raise ValueError("unsupported class weight file format")
+        class_weight = np.load(class_weight)
+    return class_weight
+
+
+def _on_device_path(inputs, targets):
+    return (inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2 and inputs.shape[1] <= 64
+            and targets.dtype == torch.int64 and targets.dim() == 1)
+
+
+class _ClassWeightCache:
+    """The class weights as a float32 tensor on the logits' device, uploaded once per device instead of per call."""
+
+    def _device_weight(self, device):
+        if self.class_weight is None:
+            return None
+        cache = self.__dict__.setdefault("_weight_cache", {})
+        if device not in cache:
+            cache[device] = torch.as_tensor(np.asarray(self.class_weight), dtype=torch.float32).to(device)
+        return cache[device]
+
+
+class FocalLoss(nn.Module, _ClassWeightCache):
+    """focal_loss.py:6-105.  CUDA float32 [n, C <= 64] logits with reduction 'mean' / 'sum' run in seg3d_focal_loss_fwd /
+    _bwd; anything else (CPU, float64, reduction 'none' with its [n_valid, C] result) is composed from torch ops.
+    Deviations: num_classes = -1 means "C of the logits" (the reference hands -1 to one_hot, which then infers the
+    width from the largest label present); on the kernel path a label outside [0, C) that is not ignore_index is
+    skipped, where one_hot raises; 'mean' over no valid row is 0 on the kernel path (NaN in torch); the composed one-hot
+    target takes the logits' dtype (focal_loss.py:77 casts it to float32, which under float64 logits leaves a float32
+    BCE term: binary_cross_entropy_with_logits returns the target's dtype)."""
+
+    def __init__(self, gamma=2.0, alpha=0.5, num_classes=-1, ignore_index=255, class_weight=None, reduction="mean",
+                 loss_name="loss_focal"):
+        super().__init__()
+        assert reduction in ("none", "mean", "sum"), "AssertionError: reduction should be 'none', 'mean' or 'sum'"
+        assert isinstance(alpha, (float, list)), "AssertionError: alpha should be of type float"
+        assert isinstance(gamma, float), "AssertionError: gamma should be of type float"
+        assert isinstance(loss_name, str), "AssertionError: loss_name should be of type str"
+        if isinstance(alpha, list):  # focal_loss.py:82 compares self.alpha >= 0: a list cannot run there either
+            raise NotImplementedError("FocalLoss: a list alpha passes the reference's assertion but not its forward")
+        self.gamma, self.alpha, self.num_classes, self.ignore_index = gamma, alpha, num_classes, ignore_index
+        self.class_weight, self.reduction = get_class_weight(class_weight), reduction
+        self._loss_name = loss_name
+
+    def forward(self, inputs, targets):
+        num_classes = inputs.size(1) if self.num_classes < 0 else self.num_classes
+        if (self.reduction != "none" and self.gamma >= 0 and num_classes == inputs.size(1)
+                and _on_device_path(inputs, targets)):
+            return ops.focal_loss(inputs, targets, gamma=self.gamma, alpha=self.alpha, ignore_index=self.ignore_index,
+                                  class_weight=self._device_weight(inputs.device), reduction=self.reduction)
+        final_weight = torch.ones(1, inputs.size(1)).type_as(inputs)
+        if self.class_weight is not None:
+            final_weight = final_weight * inputs.new_tensor(np.asarray(self.class_weight))
+        valid_mask = targets != self.ignore_index
+        inputs, targets = inputs[valid_mask], targets[valid_mask]
+        p = torch.sigmoid(inputs)
+        targets = F.one_hot(targets, num_classes).to(inputs.dtype)
+        ce_loss = F.binary_cross_entropy_with_logits(inputs, targets, reduction="none")
+        p_t = p * targets + (1 - p) * (1 - targets)
+        loss = ce_loss * ((1 - p_t) ** self.gamma)
+        if self.alpha >= 0:
+            loss = (self.alpha * targets + (1 - self.alpha) * (1 - targets)) * loss
+        loss = loss * final_weight
+        if self.reduction == "mean":
+            loss = loss.mean()
+        elif self.reduction == "sum":
+            loss = loss.sum()
+        return loss
+
+    @property
+    def loss_name(self):
+        return self._loss_name
+
+
+class DiceLoss(nn.Module, _ClassWeightCache):
+    """dice_loss.py:46-127.  On [n, C] rows the reference's per-class binary dice (dice_loss.py:9-43) is a mean over all n
+    rows of 1 - (2 p t v + smooth) / (p^e + t^e + smooth) with the valid mask v in the numerator only, so ``reduction``
+    acts on a scalar: a no-op, except that an ``avg_factor`` divides by avg_factor + eps under 'mean' and raises under
+    'sum' (loss_utils.py:43-73).  CUDA float32 [n, C <= 64] logits run in seg3d_dice_loss_fwd / _bwd, anything else is
+    composed from torch ops.  An empty input gives 0 on the kernel path (NaN in torch)."""
+
+    def __init__(self, smooth=1, exponent=2, reduction="mean", class_weight=None, loss_weight=1.0, ignore_index=255,
+                 loss_name="loss_dice"):
+        super().__init__()
+        self.smooth, self.exponent, self.reduction = smooth, exponent, reduction
+        self.class_weight = get_class_weight(class_weight)
+        self.loss_weight, self.ignore_index = loss_weight, ignore_index
+        self._loss_name = loss_name
+
+    def forward(self, pred, target, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, "none", "mean", "sum")
+        reduction = reduction_override if reduction_override else self.reduction
+        if avg_factor is not None and reduction not in ("mean", "none"):
+            raise ValueError('avg_factor can not be used with reduction="sum"')
+        divide = avg_factor is not None and reduction == "mean"
+        ignore_index = -(1 << 62) if self.ignore_index is None else self.ignore_index  # None: nothing is left out
+        if _on_device_path(pred, target) and not (divide and avg_factor < 0):
+            return ops.dice_loss(pred, target, smooth=self.smooth, exponent=self.exponent, ignore_index=ignore_index,
+                                 class_weight=self._device_weight(pred.device), loss_weight=self.loss_weight,
+                                 avg_factor=avg_factor if divide else None)
+        p = F.softmax(pred, dim=1)
+        num_classes = p.shape[1]
+        one_hot = F.one_hot(torch.clamp(target.long(), 0, num_classes - 1), num_classes=num_classes)
+        valid = (target != ignore_index).long().view(-1, 1)
+        num = p * one_hot * valid * 2 + self.smooth
+        den = p.pow(self.exponent) + one_hot.pow(self.exponent) + self.smooth
+        per_class = (1 - num / den).mean(dim=0)
+        if self.class_weight is not None:
+            per_class = per_class * p.new_tensor(np.asarray(self.class_weight))
+        keep = torch.arange(num_classes, device=p.device) != ignore_index
+        loss = self.loss_weight * (per_class * keep).sum() / num_classes
+        if divide:
+            loss = loss / (avg_factor + torch.finfo(torch.float32).eps)
+        return loss
+
+    @property
+    def loss_name(self):
+        return self._loss_name
+
+
 def build_criterion(cfg, dataset):
-    """seg3d/models/builder.py:26-40: list of (criterion, weight) in MODEL.LOSSES order."""
+    """seg3d/models/builder.py:26-40: list of (criterion, weight) in MODEL.LOSSES order.  'focal' and 'dice' go beyond the
+    reference's three keys: its package exports the two classes, its builder has no key for them."""
     losses = []
     for name in cfg.MODEL.LOSSES:
         if name == "ce":
@@ -123,6 +254,10 @@ def build_criterion(cfg, dataset):
             criterion = OHEMCrossEntropyLoss(keep_thresh=cfg.MODEL.OHEM_KEEP_THRESH, ignore_index=dataset.ignore_index)
         elif name == "lovasz":
             criterion = LovaszLoss(ignore_index=dataset.ignore_index)
+        elif name == "focal":
+            criterion = FocalLoss(num_classes=dataset.num_classes, ignore_index=dataset.ignore_index)
+        elif name == "dice":
+            criterion = DiceLoss(ignore_index=dataset.ignore_index)
         else:
             raise NotImplementedError(name)
         losses.append((criterion, cfg.MODEL.LOSSES[name]))

@@ -2301,6 +2301,105 @@ def cross_entropy(logits, labels, ignore_index=-100, keep_thresh=None):
     return _CrossEntropyFn.apply(logits, labels, ignore_index, keep_thresh if keep_thresh else 0.0)
 
 
+def _class_weight_f32(class_weight, c, device, what):
+    if class_weight is None:
+        return None
+    w = _f32c(torch.as_tensor(class_weight, dtype=torch.float32, device=device))
+    if tuple(w.shape) != (c,):
+        raise ValueError(f"{what}: class_weight must hold one value per class ({c}), got shape {tuple(w.shape)}")
+    return w
+
+
+class _FocalLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, gamma, alpha, class_weight, reduction):
+        x = _f32c(logits)
+        n, c = x.shape
+        lab = labels.contiguous()
+        stats = torch.empty((2,), dtype=torch.float32, device=x.device)
+        ws_bytes = _lib.query("seg3d_pointwise_loss_workspace_bytes", n)
+        ws = _workspace(ws_bytes, x.device)
+        _lib.call("seg3d_focal_loss_fwd", _ptr(x), _ptr(lab), n, c, int(ignore_index), float(gamma), float(alpha),
+                  _ptr(class_weight) if class_weight is not None else None, reduction, _ptr(stats), _ptr(ws), ws_bytes,
+                  _stream())
+        ctx.save_for_backward(x, lab, stats, class_weight)  # nothing [n, C]: the backward recomputes from the logits
+        ctx.args = (int(ignore_index), float(gamma), float(alpha), reduction)
+        return stats[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, lab, stats, class_weight = ctx.saved_tensors
+        ignore_index, gamma, alpha, reduction = ctx.args
+        n, c = x.shape
+        dx = torch.empty_like(x)
+        gg = _f32c(g.reshape(1))
+        _lib.call("seg3d_focal_loss_bwd", _ptr(x), _ptr(lab), _ptr(stats), _ptr(gg), n, c, ignore_index, gamma, alpha,
+                  _ptr(class_weight) if class_weight is not None else None, reduction, _ptr(dx), _stream())
+        return dx, None, None, None, None, None, None
+
+
+def focal_loss(logits, labels, gamma=2.0, alpha=0.5, ignore_index=255, class_weight=None, reduction="mean"):
+    """Sigmoid focal loss of the reference's ``FocalLoss`` (seg3d/models/losses/focal_loss.py:51-92) on float32
+    [n, C <= 64] logits and int64 labels on the GPU, one pass each way (seg3d_focal_loss_fwd / _bwd).  ``reduction``
+    'mean' (over the n_valid * C elements of the rows whose label is not ``ignore_index``; 0, not NaN, when there is
+    none) or 'sum'; ``alpha`` < 0 leaves the balance factor out.  A label outside [0, C) that is not ``ignore_index`` is
+    skipped like an ignored one, where the reference's one_hot raises."""
+    if not _loss_args_ok(logits, labels, 64):
+        raise ValueError("focal_loss: float32 [n, C <= 64] logits and int64 [n] labels on the GPU")
+    if reduction not in ("mean", "sum"):
+        raise ValueError("focal_loss: reduction 'mean' or 'sum' (the compacted 'none' result is FocalLoss's torch branch)")
+    if not float(gamma) >= 0.0:
+        raise ValueError("focal_loss: gamma >= 0")
+    w = _class_weight_f32(class_weight, logits.shape[1], logits.device, "focal_loss")
+    return _FocalLossFn.apply(logits, labels, ignore_index, gamma, alpha, w,
+                              _lib.REDUCE_MEAN if reduction == "mean" else _lib.REDUCE_SUM)
+
+
+class _DiceLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, smooth, exponent, class_weight, loss_weight, avg_factor):
+        x = _f32c(logits)
+        n, c = x.shape
+        lab = labels.contiguous()
+        out = torch.empty((1,), dtype=torch.float32, device=x.device)
+        ws_bytes = _lib.query("seg3d_pointwise_loss_workspace_bytes", n)
+        ws = _workspace(ws_bytes, x.device)
+        ctx.args = (int(ignore_index), float(smooth), float(exponent), float(loss_weight), float(avg_factor))
+        _lib.call("seg3d_dice_loss_fwd", _ptr(x), _ptr(lab), n, c, ctx.args[0], ctx.args[1], ctx.args[2],
+                  _ptr(class_weight) if class_weight is not None else None, ctx.args[3], ctx.args[4], _ptr(out), _ptr(ws),
+                  ws_bytes, _stream())
+        ctx.save_for_backward(x, lab, class_weight)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, lab, class_weight = ctx.saved_tensors
+        ignore_index, smooth, exponent, loss_weight, avg_factor = ctx.args
+        n, c = x.shape
+        dx = torch.empty_like(x)
+        gg = _f32c(g.reshape(1))
+        _lib.call("seg3d_dice_loss_bwd", _ptr(x), _ptr(lab), _ptr(gg), n, c, ignore_index, smooth, exponent,
+                  _ptr(class_weight) if class_weight is not None else None, loss_weight, avg_factor, _ptr(dx), _stream())
+        return dx, None, None, None, None, None, None, None
+
+
+def dice_loss(logits, labels, smooth=1.0, exponent=2.0, ignore_index=255, class_weight=None, loss_weight=1.0,
+              avg_factor=None):
+    """The reference's ``DiceLoss`` (seg3d/models/losses/dice_loss.py:9-43, 84-114) on float32 [n, C <= 64] logits and
+    int64 labels on the GPU, one pass each way (seg3d_dice_loss_fwd / _bwd): softmax, then per class the mean over ALL n
+    rows of 1 - (2 p t v + smooth) / (p^exponent + t^exponent + smooth), where v = [label != ignore_index] masks the
+    numerator only and t is the one-hot of the label clamped into [0, C); the classes (but ``ignore_index``) are
+    weighted, summed and divided by C.  ``avg_factor`` (>= 0): the scalar over avg_factor + eps, the reference's
+    reduction 'mean' with an avg_factor."""
+    if not _loss_args_ok(logits, labels, 64):
+        raise ValueError("dice_loss: float32 [n, C <= 64] logits and int64 [n] labels on the GPU")
+    if avg_factor is not None and not float(avg_factor) >= 0.0:
+        raise ValueError("dice_loss: avg_factor >= 0")
+    w = _class_weight_f32(class_weight, logits.shape[1], logits.device, "dice_loss")
+    return _DiceLossFn.apply(logits, labels, ignore_index, smooth, exponent, w, loss_weight,
+                             -1.0 if avg_factor is None else avg_factor)
+
+
 class _LovaszSoftmaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index, classes_mode, include, class_weight):
