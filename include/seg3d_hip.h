@@ -628,6 +628,51 @@ int seg3d_knn_grid_query(const seg3d_knn_level* levels, int32_t n_levels, const 
                          const int32_t* offset, const int32_t* new_offset, int32_t batch_size, int32_t k,
                          int32_t* idx, float* dist2, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * sampling_ext.furthestsampling_cuda -- seg3d/ops/sampling/src/sampling_cuda.cu:19-134, wrappers
+ *      seg3d/ops/sampling/sampling.py:7-86 (furthestsampling, sectorized_fps).
+ * Furthest-point sampling per segment: rows offset[i-1]:offset[i] of xyz [n,3] (contiguous float32), output slots
+ * new_offset[i-1]:new_offset[i] of idx (cumulative int32 counts, as in seg3d_knn_query).
+ *   - the first pick is the segment's first row; every further pick is the row with the largest
+ *     tmp[k] = fminf(tmp[k], d(k, last pick)), tmp starting at 1e10,
+ *     d = ((x2-x1)*(x2-x1) + (y2-y1)*(y2-y1)) + (z2-z1)*(z2-z1) in float32, every operation rounded, no FMA;
+ *   - ties go to the lowest row of the segment (the reference's winner among exactly equal distances falls out of its
+ *     shared-memory tree and changes with the block size); without exact ties both rules select the same rows;
+ *   - a segment with 0 slots writes nothing (the reference writes idx[start] unconditionally); a segment with 0 rows
+ *     and more than 0 slots gets -1 in its slots; a segment asked for more picks than it has rows keeps producing its
+ *     lowest row of distance 0;
+ *   - order (int32 [n], nullable): row k of a segment is xyz[order[k]] and the value stored is order[k]; "lowest row"
+ *     then means lowest k.  Entries must lie in [0, n): one outside is never used as an address (its row counts as
+ *     a point of running distance 0), but it can still be returned once every distance of the segment is 0.
+ *     idx holds rows of xyz, int32.
+ * One workgroup per segment, tier chosen on the device from the segment length (registers up to 16384 rows, four
+ * float planes x, y, z, tmp in the workspace above).  No allocation, no sync, capturable.  The workspace (16 bytes per
+ * row, 16-byte aligned) is required whatever the lengths.  _host: the same arithmetic and tie rule in serial C++,
+ * no HIP call. */
+size_t seg3d_furthest_sampling_workspace_bytes(int64_t n);
+int seg3d_furthest_sampling(const float* xyz, int64_t n, const int32_t* order, const int32_t* offset,
+                            const int32_t* new_offset, int32_t n_segments, int32_t* idx, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int seg3d_furthest_sampling_host(const float* xyz, int64_t n, const int32_t* order, const int32_t* offset,
+                                 const int32_t* new_offset, int32_t n_segments, int32_t* idx);
+/* The sector partition of sectorized_fps (sampling.py:49-55).
+ *   seg3d_sector_angles  angle [n] = atan2(x, y), x first as the reference writes it, evaluated in double and rounded
+ *                        once (the CUDA atan2f it replaces is not correctly rounded); minmax [batch_size, 2] = min and
+ *                        max of every sample's angles, NaN when one of them is NaN (as torch.min / torch.max: the caller
+ *                        refuses such a sample, so NaN rows are reported rather than skipped) or the sample has no row.
+ *   seg3d_sector_assign  sector_id [n] = sector_offset[b] + the first s with edge[s] <= angle < edge[s+1], or -1 (NaN
+ *                        angles); sample b has sector_offset[b+1] - sector_offset[b] sectors (sector_offset
+ *                        [batch_size + 1], cumulative) and one edge more, starting at edges[sector_offset[b] + b].
+ * seg3d_group_index over sector_id then gives the `order` and the segment offsets of seg3d_furthest_sampling. */
+int seg3d_sector_angles(const float* xyz, int64_t n, const int32_t* offset, int32_t batch_size, float* angle,
+                        float* minmax, void* stream);
+int seg3d_sector_angles_host(const float* xyz, int64_t n, const int32_t* offset, int32_t batch_size, float* angle,
+                             float* minmax);
+int seg3d_sector_assign(const float* angle, int64_t n, const int32_t* offset, int32_t batch_size, const float* edges,
+                        const int32_t* sector_offset, int32_t* sector_id, void* stream);
+int seg3d_sector_assign_host(const float* angle, int64_t n, const int32_t* offset, int32_t batch_size,
+                             const float* edges, const int32_t* sector_offset, int32_t* sector_id);
+
 /*
  * SURVEY 8(f) rank 2  WaymoDataset.prepare_voxel_labels (seg3d/datasets/waymo_dataset.py:213-246): label of a voxel =
  * most frequent label (uint8, 0..255, the ignore label counted like any other) among its points, ties to the smallest

@@ -3132,3 +3132,153 @@ def range_image_labels_host(pred, points_ri, n_classes, rows=RANGE_IMAGE_SHAPE[0
         raise RangeImageIndexError(f"{int(count[0])} points lie outside the {rows} x {cols} range image or carry a label "
                                    f"outside [0, {n_classes})")
     return img1, img2
+
+
+# ------------------------------------------------------------------------------------------ sampling_ext
+def _fps_inputs(xyz, offset, new_offset, what):
+    """-> (kind, xyz, offset, new_offset): kind 'cuda' (tensors on xyz's device, int32 offsets), or 'cpu' / 'numpy' (contiguous
+    numpy arrays, int32 offsets) for the host entries."""
+    if isinstance(xyz, torch.Tensor):
+        xyz = xyz.detach()
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32 or not xyz.is_contiguous():
+            raise _lib.Seg3dError(f"{what}: xyz must be a contiguous float32 [n, 3] tensor (sampling.py:14)")
+        if xyz.is_cuda:
+            off, noff = (_i32c(torch.as_tensor(o).to(xyz.device)) for o in (offset, new_offset))
+            return "cuda", xyz, off, noff
+        kind, xyz = "cpu", xyz.numpy()
+    else:
+        kind, xyz = "numpy", np.asarray(xyz)
+        if xyz.ndim != 2 or xyz.shape[1] != 3 or xyz.dtype != np.float32:
+            raise _lib.Seg3dError(f"{what}: xyz must be a float32 [n, 3] array")
+        xyz = np.ascontiguousarray(xyz)
+    off, noff = (np.ascontiguousarray(o.detach().cpu().numpy() if isinstance(o, torch.Tensor) else o, dtype=np.int32)
+                 for o in (offset, new_offset))
+    return kind, xyz, off, noff
+
+
+def _fps_check_counts(off, noff, n, what):
+    """off / noff: host int arrays of cumulative counts.  Raises where the kernel would have to write -1."""
+    if off.ndim != 1 or off.shape != noff.shape:
+        raise _lib.Seg3dError(f"{what}: offset and new_offset must be 1-D and of equal length")
+    sizes, new_sizes = np.diff(off, prepend=0), np.diff(noff, prepend=0)
+    if (sizes < 0).any() or (new_sizes < 0).any() or (off.size and off[-1] > n):
+        raise _lib.Seg3dError(f"{what}: offsets must be cumulative counts within the {n} rows")
+    for i in np.flatnonzero((sizes == 0) & (new_sizes > 0)):
+        raise ValueError(f"{what}: segment {int(i)} has no rows but is asked for {int(new_sizes[i])} samples")
+    return sizes, new_sizes
+
+
+def _fps_device(xyz, order, off, noff, total):
+    n, dev = xyz.shape[0], xyz.device
+    idx = torch.empty((total,), dtype=torch.int32, device=dev)
+    if total:
+        ws = _workspace(_lib.query("seg3d_furthest_sampling_workspace_bytes", n), dev)
+        _lib.call("seg3d_furthest_sampling", _ptr(xyz), n, _ptr(order), _ptr(off), _ptr(noff), off.shape[0], _ptr(idx),
+                  _ptr(ws), ws.numel(), _stream())
+    return idx
+
+
+def _fps_host(xyz, order, off, noff, total):
+    idx = np.empty((total,), dtype=np.int32)
+    if total:
+        _lib.call("seg3d_furthest_sampling_host", _hp(xyz), xyz.shape[0], _hp(order), _hp(off), _hp(noff), off.shape[0],
+                  _hp(idx))
+    return idx
+
+
+def furthestsampling(xyz, offset, new_offset):
+    """``seg3d.ops.sampling.furthestsampling`` (sampling.py:7-25): xyz contiguous float32 [n, 3], offset / new_offset
+    cumulative counts per segment -> idx int32 [new_offset[-1]], rows of xyz.  Non-differentiable, like the reference
+    Function.  CUDA tensors take seg3d_furthest_sampling (one host sync: the counts), CPU tensors and numpy arrays its
+    host twin.  Ties go to the lowest row; a segment without rows that is asked for samples raises ValueError."""
+    kind, xyz, off, noff = _fps_inputs(xyz, offset, new_offset, "furthestsampling")
+    n = xyz.shape[0]
+    if kind == "cuda":
+        b = off.shape[0]
+        counts = torch.cat([off, noff]).cpu().numpy()
+        off_h, noff_h = counts[:b], counts[b:]
+    else:
+        off_h, noff_h = off, noff
+    _fps_check_counts(off_h, noff_h, n, "furthestsampling")
+    total = int(noff_h[-1]) if noff_h.size else 0
+    if kind == "cuda":
+        return _fps_device(xyz, None, off, noff, total)
+    idx = _fps_host(xyz, None, off, noff, total)
+    return torch.from_numpy(idx) if kind == "cpu" else idx
+
+
+def _sector_plan(sizes, new_sizes, minmax, num_sectors, min_points):
+    """Host arithmetic of sectorized_fps (sampling.py:42-63): per sample the sector count, the edges -- literally
+    torch.linspace(angle.min(), angle.max() + 1e-4, S + 1) in float32 -- and the quotas (new_size // S, the remainder to the
+    last sector).  -> edges float32 [T + b], sector_offset int32 [b + 1], cumulative quotas int32 [T], (sample, sector) of
+    every global sector."""
+    edges, counts, quotas, names = [], [], [], []
+    mm = torch.from_numpy(np.ascontiguousarray(minmax, dtype=np.float32).reshape(-1, 2))
+    for i, (size, new_size) in enumerate(zip(sizes.tolist(), new_sizes.tolist())):
+        s = 1 if size < min_points else int(num_sectors)
+        if size == 0:  # nothing to sample from and (checked by the caller) nothing asked for
+            edges.append(torch.zeros((s + 1,), dtype=torch.float32))
+        else:
+            if bool(torch.isnan(mm[i]).any()):
+                raise ValueError(f"sectorized_fps: sample {i} has a row with NaN x or y (no sector can hold it)")
+            edges.append(torch.linspace(mm[i, 0], mm[i, 1] + 1e-4, s + 1, dtype=torch.float32))
+        q = [new_size // s] * s
+        q[-1] += new_size % s
+        counts.append(s)
+        quotas += q
+        names += [(i, t) for t in range(s)]
+    sector_offset = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    return (torch.cat(edges).numpy() if edges else np.zeros((0,), np.float32), sector_offset,
+            np.cumsum(quotas).astype(np.int32), names)
+
+
+def _sector_check(csr, new_sector_offset, names):
+    sizes, quotas = np.diff(csr), np.diff(new_sector_offset, prepend=0)
+    for t in np.flatnonzero((sizes == 0) & (quotas > 0)):
+        raise ValueError(f"sectorized_fps: sector {names[t][1]} of sample {names[t][0]} holds no point but is asked for "
+                         f"{int(quotas[t])} samples")
+
+
+def sectorized_fps(xyz, offset, new_offset, num_sectors, min_points=10000):
+    """``seg3d.ops.sampling.sectorized_fps`` (sampling.py:28-86): every sample with at least min_points rows is cut into
+    num_sectors sectors of equal width in atan2(x, y), each sector is sampled on its own (new_size // S picks, the
+    remainder to the last) -> idx int64 [new_offset[-1]], rows of xyz.  Angles are evaluated in double and rounded once;
+    a NaN x or y, and a sector without points that is asked for samples, raise ValueError (the reference returns rows of
+    a neighbouring sector).  On CUDA tensors: five launches and two host syncs (counts + angle ranges, sector sizes)."""
+    kind, xyz, off, noff = _fps_inputs(xyz, offset, new_offset, "sectorized_fps")
+    n, b = xyz.shape[0], off.shape[0]
+    if int(num_sectors) < 1:
+        raise _lib.Seg3dError("sectorized_fps: num_sectors must be at least 1")
+    if kind == "cuda":
+        dev = xyz.device
+        angle = torch.empty((n,), dtype=torch.float32, device=dev)
+        minmax = torch.empty((b, 2), dtype=torch.float32, device=dev)
+        _lib.call("seg3d_sector_angles", _ptr(xyz), n, _ptr(off), b, _ptr(angle), _ptr(minmax), _stream())
+        packed = torch.cat([off, noff, minmax.view(torch.int32).flatten()]).cpu().numpy()  # host sync 1
+        off_h, noff_h, minmax_h = packed[:b], packed[b:2 * b], packed[2 * b:].view(np.float32)
+    else:
+        angle, minmax_h = np.empty((n,), np.float32), np.empty((b, 2), np.float32)
+        _lib.call("seg3d_sector_angles_host", _hp(xyz), n, _hp(off), b, _hp(angle), _hp(minmax_h))
+        off_h, noff_h = off, noff
+    sizes, new_sizes = _fps_check_counts(off_h, noff_h, n, "sectorized_fps")
+    edges, sector_offset, new_sector_offset, names = _sector_plan(sizes, new_sizes, minmax_h, num_sectors, min_points)
+    n_sectors, total = len(names), int(noff_h[-1]) if b else 0
+    if kind == "cuda":
+        edges_d = torch.from_numpy(edges).to(dev)
+        ints = torch.from_numpy(np.concatenate([sector_offset, new_sector_offset])).to(dev)
+        sector_offset_d, new_sector_offset_d = ints[:b + 1], ints[b + 1:]
+        ids = torch.empty((n,), dtype=torch.int32, device=dev)
+        _lib.call("seg3d_sector_assign", _ptr(angle), n, _ptr(off), b, _ptr(edges_d), _ptr(sector_offset_d), _ptr(ids),
+                  _stream())
+        _, order, csr = group_index(ids, n_sectors, rank=False)
+        _sector_check(csr.cpu().numpy(), new_sector_offset, names)  # host sync 2
+        return _fps_device(xyz, order, csr[1:], new_sector_offset_d, total).long()
+    ids = np.empty((n,), np.int32)
+    _lib.call("seg3d_sector_assign_host", _hp(angle), n, _hp(off), b, _hp(edges), _hp(sector_offset), _hp(ids))
+    rows = np.flatnonzero(ids >= 0)
+    order = np.zeros((max(n, 1),), np.int32)  # rows grouped by sector, ascending inside a sector (seg3d_group_index's order)
+    order[:rows.size] = rows[np.argsort(ids[rows], kind="stable")]
+    csr = np.concatenate([[0], np.cumsum(np.bincount(ids[rows], minlength=n_sectors))]).astype(np.int32)
+    _sector_check(csr, new_sector_offset, names)
+    idx = _fps_host(xyz, order, np.ascontiguousarray(csr[1:]), new_sector_offset, total).astype(np.int64)
+    return torch.from_numpy(idx) if kind == "cpu" else idx
