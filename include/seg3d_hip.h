@@ -673,6 +673,66 @@ int seg3d_sector_assign(const float* angle, int64_t n, const int32_t* offset, in
 int seg3d_sector_assign_host(const float* angle, int64_t n, const int32_t* offset, int32_t batch_size,
                              const float* edges, const int32_t* sector_offset, int32_t* sector_id);
 
+/* ------------------------------------------------------------------------------------------
+ * query_and_group / interpolation -- seg3d/utils/pointops_utils.py:25-44 and :47-61 (torch indexing in the reference,
+ * no extension behind them).  xyz [n,3], new_xyz [m,3], feat [n,c], idx int32 [m,k] (rows of xyz / feat), dist float32
+ * [m,k] (seg3d_knn_query's second result after the square root); everything float32, contiguous.  1 <= k <= 64,
+ * 1 <= c <= 2^31 - 4 (a row of 3 + c floats is addressed with an int32 column; element offsets are 64-bit),
+ * m * k < 0x7F000000 (seg3d_group_index's limit); anything else is SEG3D_EINVAL.  m = 0 or n = 0: OK, nothing written.
+ *
+ * Grouping (pair p = r * k + i):
+ *     out[p, 0:3]   = xyz[idx[p]] - new_xyz[r]     one float32 subtraction per component
+ *     out[p, 3:3+c] = feat[idx[p]]                 bit copy
+ *   out is [m, k, 3 + c] -- what the reference's code returns (its docstring says (m, c+3, nsample) and promises a second
+ *   result that is never returned).  xyz = NULL: without coordinates, out is [m, k, c] and new_xyz is not read.
+ * Interpolation:
+ *     rcp[r,i] = 1.0f / (dist[r,i] + 1e-8f);  norm[r] = ((rcp[r,0] + rcp[r,1]) + ...) left to right;
+ *     weight[r,i] = rcp[r,i] / norm[r];  out[r,:] = ((0 + feat[idx[r,0]] * weight[r,0]) + feat[idx[r,1]] * weight[r,1]) + ...
+ *   left to right, product and sum rounded separately, every operation in float32.  weight [m,k] (nullable) is written
+ *   for the backward.  dist and idx carry no gradient.
+ * An index outside [0, n) (-1 included; the reference would fault or wrap) is defined and never used as an address:
+ *   grouping writes zeros to the whole slot of 3 + c values; interpolation leaves the slot out of the sum while its
+ *   reciprocal stays in norm; neither passes a gradient through it.  The slots seg3d_knn_query fills beyond a short
+ *   segment, (1e10, segment start), arrive here as an ordinary row at distance 1e5 and are treated as one, like in the
+ *   reference: reciprocal 1e-5, i.e. weight 1e-5 / norm -- about 1e-5 * d beside a real neighbour at distance d, and 1 / k
+ *   in a row made of nothing else.
+ * Backward.  pair_order / pair_offsets = `order` / `offsets` of seg3d_group_index over the flattened, sanitised idx (m * k
+ *   ids, n groups; entries outside [0, n) set to -1 first, so they are in no list), as for seg3d_knn_attention_bwd.
+ *     grouping:      dfeat[j] = sum of dout[p, 3:] and dxyz[j] = sum of dout[p, 0:3] over the pairs p with idx[p] = j, both
+ *                    from one launch and one read of the dout rows; dnew_xyz[r] = -(((0 + dout[r,0,0:3]) + dout[r,1,0:3])
+ *                    + ...) over the slots with an inside index.  NULL = not wanted (not computed, columns not read);
+ *                    with_xyz = 0: dout is [m, k, c] and dxyz / dnew_xyz must be NULL.
+ *     interpolation: dfeat[j] = sum of dout[r] * weight[p] over the pairs p = r * k + i with idx[p] = j.
+ *   ORDER OF SUMMATION (part of the contract): per source row j over its list in ascending pair index, starting from 0.
+ *   A list longer than SEG3D_POINTOPS_CHUNK = 512 entries is cut into chunks of 512 consecutive entries; every chunk is
+ *   summed on its own from 0 in ascending pair index, and the chunk sums are then added left to right in chunk order:
+ *   ((chunk 0 + chunk 1) + chunk 2) + ...  A row nobody reads gets exactly 0.  No float atomics: results are
+ *   bit-reproducible, and the _host twins (plain C++, no HIP call, host pointers, same order) return the same bits.
+ *   scratch: seg3d_pointops_scratch_bytes(m, k, width) bytes for the chunk sums, width = floats per dout row (3 + c or c
+ *   for grouping, c for interpolation); required by the device backward entries whatever the list lengths. */
+#define SEG3D_POINTOPS_CHUNK 512
+size_t seg3d_pointops_scratch_bytes(int64_t m, int32_t k, int32_t width);
+int seg3d_group_points_fwd(const float* xyz, const float* new_xyz, const float* feat, const int32_t* idx, int64_t n,
+                           int64_t m, int32_t k, int32_t c, float* out, void* stream);
+int seg3d_group_points_fwd_host(const float* xyz, const float* new_xyz, const float* feat, const int32_t* idx, int64_t n,
+                                int64_t m, int32_t k, int32_t c, float* out);
+int seg3d_group_points_bwd(const float* dout, const int32_t* idx, const int32_t* pair_order, const int32_t* pair_offsets,
+                           int64_t n, int64_t m, int32_t k, int32_t c, int32_t with_xyz, float* dxyz, float* dnew_xyz,
+                           float* dfeat, void* scratch, size_t scratch_bytes, void* stream);
+int seg3d_group_points_bwd_host(const float* dout, const int32_t* idx, const int32_t* pair_order,
+                                const int32_t* pair_offsets, int64_t n, int64_t m, int32_t k, int32_t c,
+                                int32_t with_xyz, float* dxyz, float* dnew_xyz, float* dfeat);
+int seg3d_knn_interpolate_fwd(const float* feat, const int32_t* idx, const float* dist, int64_t n, int64_t m, int32_t k,
+                              int32_t c, float* out, float* weight, void* stream);
+int seg3d_knn_interpolate_fwd_host(const float* feat, const int32_t* idx, const float* dist, int64_t n, int64_t m,
+                                   int32_t k, int32_t c, float* out, float* weight);
+int seg3d_knn_interpolate_bwd(const float* dout, const float* weight, const int32_t* idx, const int32_t* pair_order,
+                              const int32_t* pair_offsets, int64_t n, int64_t m, int32_t k, int32_t c, float* dfeat,
+                              void* scratch, size_t scratch_bytes, void* stream);
+int seg3d_knn_interpolate_bwd_host(const float* dout, const float* weight, const int32_t* idx, const int32_t* pair_order,
+                                   const int32_t* pair_offsets, int64_t n, int64_t m, int32_t k, int32_t c,
+                                   float* dfeat);
+
 /*
  * SURVEY 8(f) rank 2  WaymoDataset.prepare_voxel_labels (seg3d/datasets/waymo_dataset.py:213-246): label of a voxel =
  * most frequent label (uint8, 0..255, the ignore label counted like any other) among its points, ties to the smallest

@@ -7,7 +7,9 @@ requires CUDA(HIP) tensors and raises if the library is missing: there is no CPU
 The names exported for reference compatibility mirror ``seg3d.ops`` (seg3d/ops/__init__.py:1-6):
 ``get_inner_win_inds``, ``voxel_to_point``, ``voxel_avg_pooling``, ``voxel_max_pooling``; plus
 ``scatter`` with the ``torch_scatter.scatter(src, index, dim=0, reduce=...)`` signature used at
-vfe.py:25 and se_layer.py:25.
+vfe.py:25 and se_layer.py:25.  ``query_and_group`` / ``interpolation`` (seg3d/utils/pointops_utils.py:25-61) and
+``furthestsampling`` / ``sectorized_fps`` (seg3d/ops/sampling) are mirrored too; ``query_and_group`` with a given idx,
+``knn_interpolate`` and the two sampling calls also take CPU tensors, which run the library's host entries.
 """
 import ctypes
 import weakref
@@ -3282,3 +3284,206 @@ def sectorized_fps(xyz, offset, new_offset, num_sectors, min_points=10000):
     _sector_check(csr, new_sector_offset, names)
     idx = _fps_host(xyz, order, np.ascontiguousarray(csr[1:]), new_sector_offset, total).astype(np.int64)
     return torch.from_numpy(idx) if kind == "cpu" else idx
+
+
+# ------------------------------------------------------------------------------------------ pointops_utils
+def _pointops_kind(what, *tensors):
+    """'cuda' or 'cpu' for a set of torch tensors that must share one device (mixed devices raise)."""
+    devs = {t.device for t in tensors if t is not None}
+    if len(devs) > 1:
+        raise _lib.Seg3dError(f"{what}: all tensors must be on one device, got {sorted(str(d) for d in devs)}")
+    return "cuda" if next(iter(devs)).type == "cuda" else "cpu"
+
+
+def _pointops_rows(what, name, t, cols=None):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or \
+            (cols is not None and t.shape[1] != cols) or t.shape[1] < 1:
+        shape = tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__
+        dtype = t.dtype if isinstance(t, torch.Tensor) else None
+        raise ValueError(f"{what}: {name} must be a contiguous float32 [rows, {cols or 'c'}] tensor, got {shape} {dtype}")
+    return t
+
+
+def _pointops_idx(what, idx, m):
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.shape[0] != m or idx.dtype != torch.int32:
+        shape = tuple(idx.shape) if isinstance(idx, torch.Tensor) else type(idx).__name__
+        raise ValueError(f"{what}: idx must be an int32 [m = {m}, K] tensor (knn_query's first result), got {shape} "
+                         f"{getattr(idx, 'dtype', None)}")
+    if not 1 <= idx.shape[1] <= 64:
+        raise ValueError(f"{what}: K = {idx.shape[1]} neighbours, 1..64 supported (idx {tuple(idx.shape)})")
+    return idx.detach().contiguous()
+
+
+def _pair_lists(idx, n, kind):
+    """Inverse neighbour lists of idx [m, K] over n source rows: (order, offsets) as seg3d_group_index returns them --
+    pairs grouped by source row, ascending pair index inside a row; entries outside [0, n) are in no list."""
+    flat = idx.reshape(-1)
+    if kind == "cuda":
+        # seg3d_group_index takes ids in [0, n_groups) or -1: entries outside are set to -1 first
+        flat = torch.where((flat >= 0) & (flat < n), flat, torch.full_like(flat, -1))
+        _, order, offsets = group_index(flat, n, rank=False)
+        return order, offsets
+    ids = flat.numpy()
+    inside = np.flatnonzero((ids >= 0) & (ids < n))
+    order = np.zeros((max(ids.size, 1),), np.int32)
+    order[:inside.size] = inside[np.argsort(ids[inside], kind="stable")]
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(ids[inside], minlength=n))]).astype(np.int32)
+    return torch.from_numpy(order), torch.from_numpy(offsets)
+
+
+def _pointops_call(kind, name, *args, scratch=False):
+    """Device entry (with the current stream and, for the backward entries, their scratch: a tensor, or None where no list
+    is walked) or the _host twin (same arguments without them)."""
+    if kind == "cuda":
+        tail = () if scratch is False else (_ptr(scratch), scratch.numel() if scratch is not None else 0)
+        _lib.call(name, *args, *tail, _stream())
+    else:
+        _lib.call(name + "_host", *args)
+
+
+class _GroupPointsFn(torch.autograd.Function):
+    """query_and_group's gather (pointops_utils.py:36-44) -- seg3d_group_points_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, xyz, new_xyz, feat, idx, use_xyz):
+        kind = _pointops_kind("query_and_group", feat, idx, *((xyz, new_xyz) if use_xyz else ()))
+        n, c = feat.shape
+        m, k = idx.shape
+        w = c + 3 if use_xyz else c
+        # n = 0: every index is outside, every slot is zero (the entries write nothing then)
+        out = (torch.zeros if n == 0 else torch.empty)((m, k, w), dtype=torch.float32, device=feat.device)
+        _pointops_call(kind, "seg3d_group_points_fwd", _ptr(xyz) if use_xyz else None, _ptr(new_xyz) if use_xyz else None,
+                       _ptr(feat), _ptr(idx), n, m, k, c, _ptr(out))
+        ctx.save_for_backward(idx)
+        ctx.kind, ctx.n, ctx.c, ctx.use_xyz = kind, n, c, use_xyz
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        idx, = ctx.saved_tensors
+        kind, n, c, use_xyz = ctx.kind, ctx.n, ctx.c, ctx.use_xyz
+        m, k = idx.shape
+        need_xyz, need_new, need_feat = ctx.needs_input_grad[:3]
+        need_xyz, need_new = need_xyz and use_xyz, need_new and use_xyz
+        if not (need_xyz or need_new or need_feat):
+            return None, None, None, None, None
+        dout = _f32c(dout)
+        dev = dout.device
+        # m = 0 or n = 0: no pair passes a gradient and the entries write nothing
+        make = torch.zeros if m == 0 or n == 0 else torch.empty
+        dxyz = make((n, 3), dtype=torch.float32, device=dev) if need_xyz else None
+        dnew = make((m, 3), dtype=torch.float32, device=dev) if need_new else None
+        dfeat = make((n, c), dtype=torch.float32, device=dev) if need_feat else None
+        order = offsets = scratch = None
+        if m and n and (need_xyz or need_feat):
+            order, offsets = _pair_lists(idx, n, kind)
+            if kind == "cuda":
+                scratch = _workspace(_lib.query("seg3d_pointops_scratch_bytes", m, k, dout.shape[2]), dev)
+        if m and n:
+            _pointops_call(kind, "seg3d_group_points_bwd", _ptr(dout), _ptr(idx), _ptr(order), _ptr(offsets), n, m, k, c,
+                           1 if use_xyz else 0, _ptr(dxyz), _ptr(dnew), _ptr(dfeat), scratch=scratch)
+        return dxyz, dnew, dfeat, None, None
+
+
+def query_and_group(nsample, xyz, new_xyz, feat, idx, offset, new_offset, use_xyz=True):
+    """``query_and_group`` (pointops_utils.py:25-44): xyz [n, 3], new_xyz [m, 3] (None = xyz; the reference asserts on it
+    before it reaches its own default), feat [n, c], idx [m, nsample] rows of xyz (None = ``knn_query(nsample, ...)``,
+    CUDA tensors only) -> [m, nsample, 3 + c] = (xyz[idx] - new_xyz, feat[idx]), or [m, nsample, c] with use_xyz=False.
+    That is what the reference's code returns; its docstring promises (m, c+3, nsample) and a second result.
+    Differentiable in feat, xyz and new_xyz (fixed-order sums, no atomics).  A slot whose index is outside [0, n) is all
+    zeros and passes no gradient.  CUDA tensors run the device entries, CPU tensors the host entries."""
+    what = "query_and_group"
+    xyz = _pointops_rows(what, "xyz", xyz, 3)
+    new_xyz = xyz if new_xyz is None else _pointops_rows(what, "new_xyz", new_xyz, 3)
+    feat = _pointops_rows(what, "feat", feat)
+    if feat.shape[0] != xyz.shape[0]:
+        raise ValueError(f"{what}: feat {tuple(feat.shape)} and xyz {tuple(xyz.shape)} differ in rows")
+    if idx is None:
+        if not 1 <= int(nsample) <= 64:
+            raise ValueError(f"{what}: nsample = {nsample}, 1..64 supported")
+        if not (xyz.is_cuda and new_xyz.is_cuda):
+            raise _lib.Seg3dError(f"{what}: idx=None needs knn_query, which runs on CUDA tensors only; pass idx for CPU tensors")
+        idx, _ = knn_query(int(nsample), xyz, new_xyz, offset, new_offset)
+    idx = _pointops_idx(what, idx, new_xyz.shape[0])
+    if idx.shape[1] != int(nsample):
+        raise ValueError(f"{what}: idx {tuple(idx.shape)} does not hold nsample = {nsample} columns")
+    _pointops_kind(what, xyz, new_xyz, feat, idx)
+    return _GroupPointsFn.apply(xyz, new_xyz, feat, idx, bool(use_xyz))
+
+
+class _KnnInterpolateFn(torch.autograd.Function):
+    """interpolation's weighted sum (pointops_utils.py:54-61) -- seg3d_knn_interpolate_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, feat, idx, dist):
+        kind = _pointops_kind("knn_interpolate", feat, idx, dist)
+        n, c = feat.shape
+        m, k = idx.shape
+        need = ctx.needs_input_grad[0]
+        out = (torch.zeros if n == 0 else torch.empty)((m, c), dtype=torch.float32, device=feat.device)
+        weight = torch.empty((m, k), dtype=torch.float32, device=feat.device) if need else None
+        _pointops_call(kind, "seg3d_knn_interpolate_fwd", _ptr(feat), _ptr(idx), _ptr(dist), n, m, k, c, _ptr(out),
+                       _ptr(weight))
+        if need:
+            ctx.save_for_backward(idx, weight)
+        ctx.kind, ctx.n, ctx.c = kind, n, c
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        idx, weight = ctx.saved_tensors
+        kind, n, c = ctx.kind, ctx.n, ctx.c
+        m, k = idx.shape
+        dout = _f32c(dout)
+        if m == 0 or n == 0:
+            return torch.zeros((n, c), dtype=torch.float32, device=dout.device), None, None
+        dfeat = torch.empty((n, c), dtype=torch.float32, device=dout.device)
+        order, offsets = _pair_lists(idx, n, kind)
+        scratch = _workspace(_lib.query("seg3d_pointops_scratch_bytes", m, k, c), dout.device) if kind == "cuda" else None
+        _pointops_call(kind, "seg3d_knn_interpolate_bwd", _ptr(dout), _ptr(weight), _ptr(idx), _ptr(order), _ptr(offsets),
+                       n, m, k, c, _ptr(dfeat), scratch=scratch)
+        return dfeat, None, None
+
+
+def knn_interpolate(feat, idx, dist):
+    """The weighted sum of ``interpolation`` (pointops_utils.py:54-61) for a given neighbour table: feat [n, c], idx
+    [m, K] rows of feat, dist float32 [m, K] (knn_query's second result) -> [m, c] with
+    w = (1 / (dist + 1e-8)) / sum_K(1 / (dist + 1e-8)), out = sum_K feat[idx] * w, summed left to right in float32.
+    Differentiable in feat (fixed-order sums, no atomics); idx and dist carry no gradient.  A slot whose index is outside
+    [0, n) adds nothing but keeps its share of the norm.  CUDA tensors run the device entries, CPU tensors and numpy
+    arrays the host entries (numpy in, numpy out, no autograd)."""
+    what = "knn_interpolate"
+    as_numpy = not isinstance(feat, torch.Tensor)
+    if as_numpy:
+        feat, idx, dist = (torch.from_numpy(np.ascontiguousarray(a)) for a in (feat, idx, dist))
+    feat = _pointops_rows(what, "feat", feat)
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
+        raise ValueError(f"{what}: idx must be an int32 [m, K] tensor, got {tuple(getattr(idx, 'shape', ()))}")
+    idx = _pointops_idx(what, idx, idx.shape[0])
+    if not isinstance(dist, torch.Tensor) or tuple(dist.shape) != tuple(idx.shape) or dist.dtype != torch.float32:
+        raise ValueError(f"{what}: dist must be float32 of idx's shape {tuple(idx.shape)}, got "
+                         f"{tuple(getattr(dist, 'shape', ()))} {getattr(dist, 'dtype', None)}")
+    dist = dist.detach().contiguous()
+    _pointops_kind(what, feat, idx, dist)
+    out = _KnnInterpolateFn.apply(feat, idx, dist)
+    return out.numpy() if as_numpy else out
+
+
+def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
+    """``interpolation`` (pointops_utils.py:47-61): feat [m, c] at the rows xyz [m, 3] -> [n, c] at the rows new_xyz
+    [n, 3], inverse-distance weights over the k nearest rows: ``knn_query`` followed by ``knn_interpolate``.  CUDA
+    tensors only (knn_query).  Differentiable in feat."""
+    what = "interpolation"
+    xyz, new_xyz = _pointops_rows(what, "xyz", xyz, 3), _pointops_rows(what, "new_xyz", new_xyz, 3)
+    feat = _pointops_rows(what, "feat", feat)
+    if feat.shape[0] != xyz.shape[0]:
+        raise ValueError(f"{what}: feat {tuple(feat.shape)} and xyz {tuple(xyz.shape)} differ in rows")
+    if not 1 <= int(k) <= 64:
+        raise ValueError(f"{what}: k = {k}, 1..64 supported")
+    if not (xyz.is_cuda and new_xyz.is_cuda and feat.is_cuda):
+        raise _lib.Seg3dError(f"{what}: needs knn_query, which runs on CUDA tensors only; use knn_interpolate with a "
+                              "neighbour table for CPU tensors")
+    idx, dist = knn_query(int(k), xyz, new_xyz, offset, new_offset)
+    return knn_interpolate(feat, idx, dist)
