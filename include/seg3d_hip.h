@@ -527,8 +527,8 @@ int seg3d_batchnorm_bwd_apply(const float* dy, const float* y, const float* x, c
  */
 int seg3d_segment_reduce_fwd(const float* x, int32_t c, const int32_t* order, const int32_t* offsets,
                              int64_t n_seg, int32_t mode, float* out, int32_t* argmax, void* stream);
-/* dx [n, c] must be zero-filled by the caller for MAX; fully written for SUM/MEAN rows that belong
- * to a segment (seg_of_row = group ids, -1 rows get 0). */
+/* dx [n, c] must be zero-filled by the caller for MAX; fully written for SUM/MEAN (seg_of_row = group ids; rows
+ * whose id is outside [0, n_seg), which seg3d_group_index left out of the CSR, get 0). */
 int seg3d_segment_reduce_bwd(const float* dout, int32_t c, const int32_t* seg_of_row, int64_t n,
                              const int32_t* offsets, const int32_t* argmax, int64_t n_seg,
                              int32_t mode, float* dx, void* stream);
@@ -557,7 +557,9 @@ int seg3d_knn_attention_bwd(const float* q, const float* k, const float* v, cons
  * chunks [n_chunks][2] = (sample, first row) of every 128-row chunk in sample order, chunk_offsets [batch] = cumulative
  * chunk counts.  weights [m, classes] (kept for the backward), partials [n_chunks, classes, c] and stats
  * [batch, classes, 2] are caller-provided scratch; sums run in a fixed order (no atomics).  Backward returns d feats
- * [m, c] and d probs [m, classes]; scratch = m * classes + n_chunks * classes floats. */
+ * [m, c] and d probs [m, classes]; scratch = m * classes + n_chunks * classes floats.  offsets must not decrease and
+ * must not exceed m (the caller checks: they are host integers there); rows at or behind offsets[batch - 1] are in no
+ * sample: they add nothing to the context, their weights are left unwritten and both their gradients are 0. */
 int seg3d_class_context_fwd(const float* feats, const float* probs, const int32_t* offsets, const int32_t* chunks,
                             const int32_t* chunk_offsets, int32_t n_chunks, int32_t batch, int64_t m,
                             int32_t classes, int32_t c, float scale, float* weights, float* partials, float* stats,

@@ -138,15 +138,23 @@ __global__ __launch_bounds__(256) void ctx_bwd_rows(const float* __restrict__ fe
     }
 }
 
-// (5) + (6): d probs[r][k] = scale * (wg[r][k] - w[r][k] * delta[b][k]), delta = fixed-order sum of the chunk sums
+// (5) + (6): d probs[r][k] = scale * (wg[r][k] - w[r][k] * delta[b][k]), delta = fixed-order sum of the chunk sums.
+// Rows at or behind the last offset are in no sample: no chunk covers them, so w, wg and d feats were never written
+// there -- both gradients of such a row are set to 0 here.
 __global__ __launch_bounds__(256) void ctx_bwd_probs(const float* __restrict__ w, const float* __restrict__ wg,
                                                      const float* __restrict__ colsum, const int32_t* __restrict__ offsets,
-                                                     const int32_t* __restrict__ chunk_offsets, int batch, int K, int64_t m,
-                                                     float scale, float* __restrict__ dprobs) {
+                                                     const int32_t* __restrict__ chunk_offsets, int batch, int K, int C,
+                                                     int64_t m, float scale, float* __restrict__ dprobs,
+                                                     float* __restrict__ dfeats) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= m * K) return;
     const int64_t r = i / K;
     const int k = (int)(i - r * K);
+    if (r >= offsets[batch - 1]) {
+        dprobs[i] = 0.f;
+        for (int c = k; c < C; c += K) dfeats[r * C + c] = 0.f;
+        return;
+    }
     const int b = sample_of(offsets, batch, r);
     const int c0 = b ? chunk_offsets[b - 1] : 0, c1 = chunk_offsets[b];
     float delta = 0.f;
@@ -196,18 +204,26 @@ int seg3d_class_context_bwd(const float* feats, const float* weights, const floa
                             int32_t classes, int32_t c, float scale, float* dfeats, float* dprobs,
                             float* scratch /*[m * classes + n_chunks * classes]*/, void* stream) {
     if (batch < 0 || m < 0 || n_chunks < 0 || bad_shape(classes, c)) return SEG3D_EINVAL;
-    if (batch == 0 || m == 0) return SEG3D_OK;
-    if (!feats || !weights || !dcontext || !offsets || !chunks || !chunk_offsets || !dfeats || !dprobs || !scratch)
+    if (m == 0) return SEG3D_OK;
+    if (!dfeats || !dprobs) return SEG3D_EINVAL;
+    if (batch == 0) {  // no sample: every row is behind the last offset
+        SEG3D_CHECK_HIP(hipMemsetAsync(dfeats, 0, (size_t)m * c * sizeof(float), as_stream(stream)));
+        SEG3D_CHECK_HIP(hipMemsetAsync(dprobs, 0, (size_t)m * classes * sizeof(float), as_stream(stream)));
+        return SEG3D_OK;
+    }
+    if (!feats || !weights || !dcontext || !offsets || (n_chunks > 0 && !chunks) || !chunk_offsets || !dfeats || !dprobs || !scratch)
         return SEG3D_EINVAL;
     hipStream_t st = as_stream(stream);
     float* wg = scratch;
     float* colsum = scratch + m * classes;
     const size_t smem = ((size_t)classes * c + (size_t)kChunk * kMaxK) * sizeof(float);
-    hipLaunchKernelGGL(ctx_bwd_rows, dim3((unsigned)n_chunks), dim3(256), smem, st, feats, weights, dcontext, offsets,
-                       reinterpret_cast<const int2*>(chunks), classes, c, dfeats, wg, colsum);
-    SEG3D_CHECK_LAUNCH();
+    if (n_chunks > 0) {
+        hipLaunchKernelGGL(ctx_bwd_rows, dim3((unsigned)n_chunks), dim3(256), smem, st, feats, weights, dcontext, offsets,
+                           reinterpret_cast<const int2*>(chunks), classes, c, dfeats, wg, colsum);
+        SEG3D_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(ctx_bwd_probs, dim3((unsigned)ceil_div64(m * classes, 256)), dim3(256), 0, st, weights, wg, colsum, offsets,
-                       chunk_offsets, batch, classes, m, scale, dprobs);
+                       chunk_offsets, batch, classes, c, m, scale, dprobs, dfeats);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }

@@ -68,18 +68,20 @@ __global__ __launch_bounds__(kThreads) void seg_reduce_kernel(const float* __res
     }
 }
 
-// SUM / MEAN backward: dx[i] = dout[seg[i]] * (1 or 1/count)
+// SUM / MEAN backward: dx[i] = dout[seg[i]] * (1 or 1/count); rows whose id is outside [0, n_seg) were in no segment
+// (seg3d_group_index skips them) and get 0
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void seg_bwd_bcast_kernel(const float* __restrict__ dout, int c,
                                                                  const int32_t* __restrict__ seg_of_row, int64_t n,
-                                                                 const int32_t* __restrict__ offsets, float* __restrict__ dx) {
+                                                                 const int32_t* __restrict__ offsets, int64_t n_seg,
+                                                                 float* __restrict__ dx) {
     const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (t >= n * c) return;
     const int64_t i = t / c;
     const int ch = (int)(t - i * c);
     const int32_t s = seg_of_row[i];
     float g = 0.f;
-    if (s >= 0) {
+    if (s >= 0 && s < n_seg) {
         g = dout[(int64_t)s * c + ch];
         if (MODE == SEG3D_REDUCE_MEAN) g = g / (float)(offsets[s + 1] - offsets[s]);
     }
@@ -184,9 +186,14 @@ int seg3d_segment_reduce_fwd(const float* x, int32_t c, const int32_t* order, co
 int seg3d_segment_reduce_bwd(const float* dout, int32_t c, const int32_t* seg_of_row, int64_t n, const int32_t* offsets,
                              const int32_t* argmax, int64_t n_seg, int32_t mode, float* dx, void* stream) {
     if (n < 0 || n_seg < 0 || c <= 0) return SEG3D_EINVAL;
-    if (n == 0 || n_seg == 0) return SEG3D_OK;
-    if (!dout || !dx) return SEG3D_EINVAL;
+    if (n == 0) return SEG3D_OK;
+    if (!dx) return SEG3D_EINVAL;
     hipStream_t st = as_stream(stream);
+    if (n_seg == 0) {  // no segment, no gradient (the MAX caller hands in zeros already)
+        if (mode != SEG3D_REDUCE_MAX) SEG3D_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)n * c * sizeof(float), st));
+        return SEG3D_OK;
+    }
+    if (!dout) return SEG3D_EINVAL;
     if (mode == SEG3D_REDUCE_MAX) {
         if (!argmax) return SEG3D_EINVAL;
         hipLaunchKernelGGL(seg_bwd_max_kernel, dim3((unsigned)ceil_div64(n_seg * c, kThreads)), dim3(kThreads), 0, st, dout,
@@ -194,11 +201,11 @@ int seg3d_segment_reduce_bwd(const float* dout, int32_t c, const int32_t* seg_of
     } else if (mode == SEG3D_REDUCE_MEAN) {
         if (!seg_of_row || !offsets) return SEG3D_EINVAL;
         hipLaunchKernelGGL(seg_bwd_bcast_kernel<SEG3D_REDUCE_MEAN>, dim3((unsigned)ceil_div64(n * c, kThreads)),
-                           dim3(kThreads), 0, st, dout, c, seg_of_row, n, offsets, dx);
+                           dim3(kThreads), 0, st, dout, c, seg_of_row, n, offsets, n_seg, dx);
     } else if (mode == SEG3D_REDUCE_SUM) {
         if (!seg_of_row) return SEG3D_EINVAL;
         hipLaunchKernelGGL(seg_bwd_bcast_kernel<SEG3D_REDUCE_SUM>, dim3((unsigned)ceil_div64(n * c, kThreads)),
-                           dim3(kThreads), 0, st, dout, c, seg_of_row, n, offsets, dx);
+                           dim3(kThreads), 0, st, dout, c, seg_of_row, n, offsets, n_seg, dx);
     } else {
         return SEG3D_EINVAL;
     }

@@ -1402,6 +1402,8 @@ class _SpanMeanFn(torch.autograd.Function):
             lo = hi
         if lo < ctx.rows:
             pieces.append(g.new_zeros((ctx.rows - lo, g.shape[1])))
+        if not pieces:  # no rows at all
+            return g.new_zeros((ctx.rows, g.shape[1])), None
         return (torch.cat(pieces) if len(pieces) != 1 else pieces[0].contiguous()), None
 
 
@@ -1919,8 +1921,13 @@ class _SegmentReduceFn(torch.autograd.Function):
         n, c = x.shape
         out = torch.empty((seg.n_segments, c), dtype=torch.float32, device=x.device)
         arg = torch.empty((seg.n_segments, c), dtype=torch.int32, device=x.device) if mode == REDUCE_MAX else None
-        _lib.call("seg3d_segment_reduce_fwd", _ptr(x), c, _ptr(seg.order), _ptr(seg.offsets), seg.n_segments, mode,
-                  _ptr(out), _ptr(arg), _stream())
+        if n == 0:  # no rows (and no pointers to hand over): every segment is empty
+            out.zero_()
+            if arg is not None:
+                arg.fill_(-1)
+        else:
+            _lib.call("seg3d_segment_reduce_fwd", _ptr(x), c, _ptr(seg.order), _ptr(seg.offsets), seg.n_segments, mode,
+                      _ptr(out), _ptr(arg), _stream())
         ctx.seg, ctx.mode, ctx.arg, ctx.n = seg, mode, arg, n
         return out
 
@@ -1971,6 +1978,8 @@ class _GatherRowsFn(torch.autograd.Function):
         dout = _f32c(dout)
         seg = ctx.seg if ctx.seg is not None else SegmentIndex(ctx.ids, ctx.m)
         c = dout.shape[1]
+        if dout.shape[0] == 0:
+            return torch.zeros((ctx.m, c), dtype=torch.float32, device=dout.device), None, None
         dfeat = torch.empty((ctx.m, c), dtype=torch.float32, device=dout.device)
         _lib.call("seg3d_segment_reduce_fwd", _ptr(dout), c, _ptr(seg.order), _ptr(seg.offsets), ctx.m, REDUCE_SUM,
                   _ptr(dfeat), None, _stream())
@@ -2193,10 +2202,16 @@ def class_context_fits(classes, channels):
 def class_context(feats, probs, row_offsets, scale=1.0):
     """context [B, classes, C] = per sample (rows offsets[b-1] .. offsets[b]) softmax over the sample's rows of
     scale * probs[:, k], times feats (SpatialGatherModule, seg3d/models/layers/ocr.py:10-36), any batch size in one
-    launch sequence, differentiable w.r.t. feats and probs.  row_offsets: cumulative row counts per sample (python ints)."""
+    launch sequence, differentiable w.r.t. feats and probs.  row_offsets: cumulative row counts per sample (python ints);
+    rows at or behind the last offset are in no sample: they add nothing and get zero gradients."""
     _need_gpu(feats, probs)
+    if feats.dim() != 2 or probs.dim() != 2 or probs.shape[0] != feats.shape[0]:
+        raise _lib.Seg3dError("class_context: feats [m, C] and probs [m, classes] expected")
     if not class_context_fits(probs.shape[1], feats.shape[1]):
         raise _lib.Seg3dError("class_context: at most 32 classes, channels a multiple of 4, classes * channels <= 12288")
+    offs = [int(o) for o in row_offsets]
+    if any(hi < lo for lo, hi in zip([0] + offs, offs)) or (offs and offs[-1] > feats.shape[0]):
+        raise _lib.Seg3dError("class_context: row_offsets must be cumulative counts: not decreasing, at most the number of rows")
     return _ClassContextFn.apply(feats, probs, class_context_plan(row_offsets, feats.device), float(scale))
 
 

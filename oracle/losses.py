@@ -41,7 +41,7 @@ def lovasz_softmax(logits, labels, ignore_index=255, classes="present", class_we
     chosen = range(probs.shape[1]) if classes in ("present", "all") else classes
     terms = []
     for c in chosen:
-        fg = (y == c).float()
+        fg = (y == c).to(probs.dtype)
         if classes == "present" and fg.sum() == 0:
             continue
         err, order = torch.sort((fg - probs[:, c]).abs(), descending=True)
