@@ -1197,6 +1197,52 @@ int seg3d_range_image_labels(const void* pred, int32_t pred_bytes, const int32_t
 int seg3d_range_image_labels_host(const void* pred, int32_t pred_bytes, const int32_t* points_ri, int64_t n, int32_t rows,
                                   int32_t cols, int32_t n_classes, int32_t* image1, int32_t* image2, int32_t* n_outside);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-point image features (csrc/image_features.hip): the producer of `point_image_features`, the input of
+ * DeepFusionBlock.
+ *
+ * seg3d_point_image_features -- the lookup loop of tools/extract_image_feature.py:84-100.  `table` is a HOST pointer;
+ * the kernel receives it by value.  Map m is camera m's feature map: `channels` values per pixel of float32
+ * (elem_bytes 4) or float16 (2), element (c, y, x) at data[c * channel_stride + y * row_stride + x * col_stride] --
+ * strides in ELEMENTS, so a (C, H, W) array as the image model returns it, an HWC array and a non-contiguous view are
+ * all read in place.  data NULL = the camera is absent (:19-21, the image could not be read).
+ * rows: the raw lidar file, [n, stride] of float32 (point_bytes 4) or float64 (8); columns cp_col .. cp_col + 5 hold
+ * (camera name, x, y, camera name, x, y), cp_col = 6 in the parser's layout (:90-97).  A value v becomes an integer as
+ * Python's int(v): truncation toward zero (7.9 -> 7; -0.5 -> 0, a valid coordinate).  Per row:
+ *   take the first projection if name - 1 is in [0, n_maps) and that map is present (:90-93), otherwise the second
+ *   under the same test (:94-97), otherwise the row misses.  With the first camera present the second is never
+ *   consulted (if / elif).  Name 0, "no projection", gives -1 and misses.
+ *   hit  (:99-100): out_dense[i, c] = float32(map element (c, y, x)) for c < channels, out_camera[i] = the camera index.
+ *   miss:           out_dense[i, :] = 0, out_camera[i] = -1.
+ * out_dense float32 [n, channels] and out_camera int32 [n] are written in full; the caller does not pre-zero them.
+ * Outside pixels: a chosen camera whose (x, y) is outside [0, width) x [0, height), or a non-finite value or
+ * |v| >= 2^31 in a column the decision reads, makes the row a miss and is counted in n_outside (int32 [1], device memory
+ * for the device entry; the entry zeroes it first).  The reference raises IndexError for indices that are too large and
+ * lets negative ones wrap around the image; refusing negative ones is a deliberate deviation.
+ * SEG3D_EINVAL before any launch: channels outside 1..64, n_maps outside 1..8, elem_bytes not 2 / 4, point_bytes not
+ * 4 / 8, cp_col < 0 or cp_col + 6 > stride, n < 0 or n > INT32_MAX, a present map with height, width or a stride < 1,
+ * a NULL rows / out_dense / out_camera / n_outside with n > 0.  n == 0 returns 0 and launches nothing; a table whose
+ * maps are all absent is legal (every row misses).  All offsets are 64-bit.  No allocation, no synchronisation.
+ * seg3d_point_image_features_host: the same contract on HOST pointers, plain C++ without a HIP call; the same integers
+ * and the same floats bit for bit (everything is a copy; float16 -> float32 is exact).
+ */
+#define SEG3D_IMAGE_MAX_CAMERAS 8
+typedef struct {
+  const void* data; /* NULL = camera absent */
+  int32_t height, width;
+  int64_t channel_stride, row_stride, col_stride; /* in elements, each >= 1 */
+} seg3d_feature_map;
+typedef struct {
+  int32_t n_maps, channels, elem_bytes /* 4 float32, 2 float16 */, reserved;
+  seg3d_feature_map maps[SEG3D_IMAGE_MAX_CAMERAS];
+} seg3d_feature_map_table;
+int seg3d_point_image_features(const seg3d_feature_map_table* table, const void* rows, int32_t point_bytes, int64_t n,
+                               int32_t stride, int32_t cp_col, float* out_dense, int32_t* out_camera, int32_t* n_outside,
+                               void* stream);
+int seg3d_point_image_features_host(const seg3d_feature_map_table* table, const void* rows, int32_t point_bytes,
+                                    int64_t n, int32_t stride, int32_t cp_col, float* out_dense, int32_t* out_camera,
+                                    int32_t* n_outside);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 49
+ABI_VERSION = 50
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -186,6 +186,8 @@ SIGNATURES = {
     "seg3d_range_image_workspace_bytes": (_sz, [_i32, _i32]),
     "seg3d_range_image_labels": (ctypes.c_int, [_p, _i32, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _sz, _p]),
     "seg3d_range_image_labels_host": (ctypes.c_int, [_p, _i32, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
+    "seg3d_point_image_features": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p]),
+    "seg3d_point_image_features_host": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
 }
 
 _ERR = {EINVAL: "SEG3D_EINVAL (bad argument)", EWORKSPACE: "SEG3D_EWORKSPACE (workspace too small)",

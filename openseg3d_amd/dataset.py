@@ -27,7 +27,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-from . import augment, ops, scene
+from . import augment, image_features, ops, scene
 from ._lib import Seg3dError
 from .batch import VoxelGenerator
 
@@ -155,7 +155,15 @@ class WaymoDataset(Dataset):
         return np.load(os.path.join(self.data_root, 'lidar', filename + '.npy'))
 
     def _raw_image_features(self, filename):
-        """The pickled dict row -> feature, flattened to (rows int32 [K], feats float32 [K, F])."""
+        """(rows int32 [K], feats float32 [K, F]) of a frame.  ``image_feature/<name>.npz`` (image_features.save_packed:
+        the two arrays as they are, no pickle, no loop) is read when it exists; otherwise the reference's pickled dict
+        row -> feature, ``<name>.npy``, is flattened as before.  When both files exist the packed one wins."""
+        packed = os.path.join(self.data_root, 'image_feature', filename + '.npz')
+        if os.path.exists(packed):
+            rows, feats = image_features.load_packed(packed)
+            if feats.shape[1] != self.dim_image_feature:
+                raise Seg3dError(f"{packed}: {feats.shape[1]} features per row, DIM_IMAGE_FEATURE is {self.dim_image_feature}")
+            return rows, feats
         d = np.load(os.path.join(self.data_root, 'image_feature', filename + '.npy'), allow_pickle=True).item()
         rows = np.fromiter(d.keys(), dtype=np.int64, count=len(d)).astype(np.int32)
         feats = np.zeros((len(d), self.dim_image_feature), dtype=np.float32)

@@ -3151,6 +3151,147 @@ def range_image_labels_host(pred, points_ri, n_classes, rows=RANGE_IMAGE_SHAPE[0
     return img1, img2
 
 
+# ------------------------------------------------------------------------------------------ image features (csrc/image_features.hip)
+IMAGE_MAX_CAMERAS = 8
+IMAGE_MAX_CHANNELS = 64
+
+
+class FeatureMap(ctypes.Structure):
+    """seg3d_feature_map (include/seg3d_hip.h)."""
+    _fields_ = [("data", ctypes.c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("channel_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("col_stride", ctypes.c_int64)]
+
+
+class FeatureMapTable(ctypes.Structure):
+    """seg3d_feature_map_table: up to 8 cameras; ``arrays`` keeps the maps alive."""
+    _fields_ = [("n_maps", ctypes.c_int32), ("channels", ctypes.c_int32), ("elem_bytes", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("maps", FeatureMap * IMAGE_MAX_CAMERAS)]
+
+
+class ImageFeatureIndexError(IndexError, _lib.Seg3dError):
+    """A chosen camera's pixel lies outside its feature map, or a projection column holds no int32."""
+
+
+def feature_map_table(maps, host, device=None, channels=None):
+    """``maps``: the reference's ``image_feature_maps`` -- a dict {camera_id: (C, H, W) array} with absent cameras simply
+    missing (extract_image_feature.py:11-25) -- or a sequence indexed by camera id with None for an absent camera.
+    Arrays are float32 / float16 of one dtype and one C, numpy (host entry) or CUDA tensors on ``device``, with ANY
+    strides: a transposed HWC array or a channel slice is described by its strides and read in place.  channels: C when no
+    camera is present (the table is then legal and every row misses)."""
+    if isinstance(maps, dict):
+        keys = list(maps)
+        if any(not isinstance(k, (int, np.integer)) or k < 0 or k >= IMAGE_MAX_CAMERAS for k in keys):
+            raise _lib.Seg3dError(f"point_image_features: camera ids are ints in [0, {IMAGE_MAX_CAMERAS})")
+        seq = [maps.get(k) for k in range(max(keys) + 1)] if keys else [None]
+    else:
+        seq = list(maps) or [None]
+        if len(seq) > IMAGE_MAX_CAMERAS:
+            raise _lib.Seg3dError(f"point_image_features: at most {IMAGE_MAX_CAMERAS} cameras")
+    present = [m for m in seq if m is not None]
+    f32, f16 = (np.float32, np.float16) if host else (torch.float32, torch.float16)
+    t = FeatureMapTable()
+    t.n_maps, t.arrays = len(seq), present
+    if not present:
+        if channels is None:
+            raise _lib.Seg3dError("point_image_features: no camera is present; pass channels=C")
+        t.channels, t.elem_bytes = int(channels), 4
+        return t
+    dtype, C = present[0].dtype, int(present[0].shape[0]) if present[0].ndim == 3 else -1
+    if channels is not None and int(channels) != C:
+        raise _lib.Seg3dError(f"point_image_features: channels={channels} but the maps hold {C}")
+    if dtype not in (f32, f16) or not 1 <= C <= IMAGE_MAX_CHANNELS:
+        raise _lib.Seg3dError(f"point_image_features: maps are float32 / float16 (C, H, W) arrays with C in [1, {IMAGE_MAX_CHANNELS}]")
+    t.channels, t.elem_bytes = C, 4 if dtype == f32 else 2
+    for k, m in enumerate(seq):
+        if m is None:
+            continue
+        ok = isinstance(m, np.ndarray) if host else (isinstance(m, torch.Tensor) and m.is_cuda and m.device == device)
+        if not ok:
+            raise _lib.Seg3dError("point_image_features: maps are numpy arrays (host entry) or CUDA tensors on the rows' "
+                                  "device (device entry)")
+        if m.ndim != 3 or m.dtype != dtype or int(m.shape[0]) != C or m.shape[1] < 1 or m.shape[2] < 1:
+            raise _lib.Seg3dError("point_image_features: all present maps are (C, H, W) with one C and one dtype, H, W >= 1")
+        strides = [s // m.itemsize for s in m.strides] if host else list(m.stride())
+        # a stride is used only along an axis longer than 1; anything >= 1 describes the same elements
+        strides = [int(s) if int(d) > 1 else max(int(s), 1) for s, d in zip(strides, m.shape)]
+        if min(strides) < 1:
+            raise _lib.Seg3dError("point_image_features: maps with zero or negative strides (broadcast, flipped) are not "
+                                  "read in place; pass a copy")
+        e = t.maps[k]
+        e.data = m.ctypes.data if host else m.data_ptr()
+        e.height, e.width = int(m.shape[1]), int(m.shape[2])
+        e.channel_stride, e.row_stride, e.col_stride = strides
+    return t
+
+
+def _feature_rows(rows, host, cp_col):
+    f32, f64 = (np.float32, np.float64) if host else (torch.float32, torch.float64)
+    if not (isinstance(rows, np.ndarray) if host else isinstance(rows, torch.Tensor)):
+        raise _lib.Seg3dError("point_image_features takes a CUDA tensor, point_image_features_host a numpy array")
+    if rows.ndim != 2 or rows.dtype not in (f32, f64):
+        raise _lib.Seg3dError("point_image_features: rows is a float32 / float64 [n, stride] array (the raw lidar file)")
+    if cp_col < 0 or cp_col + 6 > rows.shape[1]:
+        raise _lib.Seg3dError(f"point_image_features: columns {cp_col}..{cp_col + 5} do not lie inside rows of {rows.shape[1]}")
+    n = int(rows.shape[0])
+    if n:
+        item = rows.itemsize if host else rows.element_size()
+        rs, cs = (rows.strides[0] // item, rows.strides[1] // item) if host else (rows.stride(0), rows.stride(1))
+        if cs != 1 or (n > 1 and rs < rows.shape[1]):
+            rows = np.ascontiguousarray(rows) if host else rows.contiguous()
+            rs = rows.shape[1]
+        stride = int(rs) if n > 1 else int(rows.shape[1])
+    else:
+        stride = int(rows.shape[1])
+    return rows, n, stride, 4 if rows.dtype == f32 else 8
+
+
+def _image_feature_error(bad):
+    return ImageFeatureIndexError(f"{bad} rows project outside their camera's feature map or hold a projection value that "
+                                  "is no int32 (extract_image_feature.py:100 raises IndexError or wraps around)")
+
+
+def point_image_features(rows, maps, cp_col=6, check=True, channels=None):
+    """seg3d_point_image_features (tools/extract_image_feature.py:84-100): ``rows`` the raw lidar rows, a float32 /
+    float64 [n, stride] CUDA tensor whose columns cp_col .. cp_col + 5 are (camera name, x, y, camera name, x, y);
+    ``maps`` as ``feature_map_table`` takes them, on the same device.  Returns (dense float32 [n, C], camera int32 [n]):
+    a row's features from the first projection whose camera is present, zeros and -1 where neither is.  check: read the
+    outside-pixel count back (one host sync) and raise ImageFeatureIndexError where the reference would raise
+    IndexError (or wrap a negative index); check=False returns (dense, camera, count tensor)."""
+    _need_gpu(rows)
+    rows, n, stride, pb = _feature_rows(rows, False, int(cp_col))
+    dev = rows.device
+    table = feature_map_table(maps, False, dev, channels)
+    dense = torch.empty((n, table.channels), dtype=torch.float32, device=dev)
+    camera = torch.empty((n,), dtype=torch.int32, device=dev)
+    count = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("seg3d_point_image_features", ctypes.byref(table), _ptr(rows) if n else None, pb, n, stride, int(cp_col),
+                  _ptr(dense), _ptr(camera), _ptr(count), _stream())
+    if not check:
+        return dense, camera, count
+    bad = int(count.item())
+    if bad:
+        raise _image_feature_error(bad)
+    return dense, camera
+
+
+def point_image_features_host(rows, maps, cp_col=6, check=True, channels=None):
+    """seg3d_point_image_features_host: the same on numpy arrays (plain C++ of the same library, no HIP call), bit for
+    bit.  check=False returns (dense, camera, count int32 [1])."""
+    rows, n, stride, pb = _feature_rows(rows, True, int(cp_col))
+    table = feature_map_table(maps, True, None, channels)
+    dense = np.empty((n, table.channels), dtype=np.float32)
+    camera = np.empty((n,), dtype=np.int32)
+    count = np.zeros((1,), dtype=np.int32)
+    _lib.call("seg3d_point_image_features_host", ctypes.byref(table), _hp(rows) if n else None, pb, n, stride, int(cp_col),
+              _hp(dense), _hp(camera), _hp(count))
+    if not check:
+        return dense, camera, count
+    if int(count[0]):
+        raise _image_feature_error(int(count[0]))
+    return dense, camera
+
+
 # ------------------------------------------------------------------------------------------ sampling_ext
 def _fps_inputs(xyz, offset, new_offset, what):
     """-> (kind, xyz, offset, new_offset): kind 'cuda' (tensors on xyz's device, int32 offsets), or 'cpu' / 'numpy' (contiguous
