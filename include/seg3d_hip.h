@@ -783,6 +783,46 @@ int seg3d_lovasz_softmax_bwd(const float* logits, const float* coef, const float
                              int64_t n, int32_t c, float* dlogits, void* stream);
 
 /*
+ * The whole criterion of tools/train.py:71-110 in one call: up to four heads (point, voxel, auxiliary voxel logits, each
+ * [n_h, c <= 64] with int64 labels; sum n_h * c < 2^31), the 'ce' / 'ohem_ce' term and / or the 'lovasz' term as the two
+ * entries above compute them ('present' classes, no class weights), and
+ *   loss = sum over the heads in table order, per head ce then lovasz, of (head weight * term) * term weight
+ * in float32, starting from 0: the sequence compute_loss runs.  Loss and gradients carry the bits of the per-term entries;
+ * one row pass, ONE device sort of (head, class, error) keys and one finalize replace theirs.
+ *   terms    SEG3D_CRITERION_CE | SEG3D_CRITERION_LOVASZ (at least one)
+ *   forward  lse [sum n] and coef [sum n, c] (rows of the heads one after the other; kept for backward, lse only with the
+ *            CE term, coef only with the Lovasz term), stats [n_heads][SEG3D_CRITERION_STATS_STRIDE] = per head {ce mean,
+ *            ce count, lovasz loss, classes averaged, d lovasz / d loss_class [64]}, loss [1]
+ *   backward dlogits[h] [n_h, c] = d loss / d logits of head h for the upstream gradient grad_out[0]: the float32 sum of the
+ *            two terms' gradients, each rounded as its own backward rounds it
+ * Logits must not be NaN: the per-term Lovasz entry then returns NaN, this one an undefined (possibly finite) loss; all
+ * accesses stay in bounds either way.
+ * seg3d_criterion_workspace_bytes: 0 = invalid arguments, or (Lovasz term) no device visible.  Invalid arguments and a
+ * workspace too small for the call's own buffers are refused before anything is enqueued.
+ */
+#define SEG3D_CRITERION_MAX_HEADS 4
+#define SEG3D_CRITERION_CE 1
+#define SEG3D_CRITERION_LOVASZ 2
+#define SEG3D_CRITERION_STATS_STRIDE 68
+typedef struct {
+    const float* logits;   /* [n, c] */
+    const int64_t* labels; /* [n] */
+    int64_t n;
+    float weight;          /* head weight (MODEL.AUX_LOSS_WEIGHT on the auxiliary head, 1 elsewhere) */
+} seg3d_criterion_head;
+typedef struct {
+    int32_t n_heads;
+    seg3d_criterion_head heads[SEG3D_CRITERION_MAX_HEADS];
+} seg3d_criterion_table;
+size_t seg3d_criterion_workspace_bytes(const seg3d_criterion_table* heads, int32_t c, int32_t terms);
+int seg3d_criterion_fwd(const seg3d_criterion_table* heads, int32_t c, int32_t terms, int64_t ignore_index,
+                        float keep_thresh, float w_ce, float w_lovasz, float* lse, float* coef, float* stats, float* loss,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int seg3d_criterion_bwd(const seg3d_criterion_table* heads, int32_t c, int32_t terms, float w_ce, float w_lovasz,
+                        const float* lse, const float* coef, const float* stats, const float* grad_out,
+                        float* const* dlogits, void* stream);
+
+/*
  * FocalLoss (seg3d/models/losses/focal_loss.py:51-92) on logits [n, c <= 64] with int64 labels, sigmoid focal loss against
  * the one-hot label.  Valid rows: label != ignore_index; a label outside [0, c) is skipped and not counted either, as in
  * seg3d_cross_entropy_fwd (the reference's one_hot raises there -- the one deviation).  Per element of a valid row, with

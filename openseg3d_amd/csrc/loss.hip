@@ -7,12 +7,12 @@
 //   forward : lse[r] = log sum exp(x[r]) on counted rows, +inf on the others;
 //             acc[0] += lse[r] - x[r][label],  acc[1] += 1                                   (per-block partials)
 //   backward: dx[r][c] = (softmax(x[r])[c] - [c == label]) * g / count on counted rows, 0 elsewhere
-#include "common.hpp"
+#include "criterion_device.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 1024;
+using crit::kMaxBlocks;
+using crit::kThreads;
 
 __global__ __launch_bounds__(kThreads) void ce_fwd_kernel(const float* __restrict__ x, const int64_t* __restrict__ label,
                                                           int64_t n, int c, int64_t ignore_index, float keep_thresh,
@@ -21,67 +21,31 @@ __global__ __launch_bounds__(kThreads) void ce_fwd_kernel(const float* __restric
     float loss = 0.f, cnt = 0.f;
     for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < n; r += (int64_t)gridDim.x * kThreads) {
         const float* row = x + r * c;
-        float m = row[0];
-        for (int j = 1; j < c; ++j) m = fmaxf(m, row[j]);
-        float s = 0.f;
-        for (int j = 0; j < c; ++j) s += expf(row[j] - m);
-        const float l = m + logf(s);
+        float m, s, l;
+        crit::softmax_stats(row, c, &m, &s);
         const int64_t y = label[r];
-        bool counted = y != ignore_index && y >= 0 && y < c;
-        if (counted && keep_thresh > 0.f) counted = expf(row[y] - m) / s < keep_thresh;  // softmax(x)[y] < keep_thresh
+        const bool counted = crit::ce_row(row, c, y, ignore_index, keep_thresh, m, s, &l);
         lse[r] = counted ? l : INFINITY;
         if (counted) {
             loss += l - row[y];
             cnt += 1.f;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        loss += __shfl_xor(loss, off, SEG3D_WAVE);
-        cnt += __shfl_xor(cnt, off, SEG3D_WAVE);
-    }
-    __shared__ float red[2][kThreads / 64];
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = loss;
-        red[1][threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
+    crit::block_sum2(loss, cnt);
     if (threadIdx.x == 0) {
-        float a = 0.f, b = 0.f;
-        for (int w = 0; w < kThreads / 64; ++w) {
-            a += red[0][w];
-            b += red[1][w];
-        }
-        part[2 * blockIdx.x] = a;
-        part[2 * blockIdx.x + 1] = b;
+        part[2 * blockIdx.x] = loss;
+        part[2 * blockIdx.x + 1] = cnt;
     }
 }
 
 // out[0] = mean loss over counted rows (0 when none), out[1] = count; fixed summation order
 __global__ __launch_bounds__(kThreads) void ce_finalize_kernel(const float* __restrict__ part, int nblocks,
                                                                float* __restrict__ out) {
-    float a = 0.f, b = 0.f;
-    for (int i = threadIdx.x; i < nblocks; i += kThreads) {
-        a += part[2 * i];
-        b += part[2 * i + 1];
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, SEG3D_WAVE);
-        b += __shfl_xor(b, off, SEG3D_WAVE);
-    }
-    __shared__ float red[2][kThreads / 64];
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = a;
-        red[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
+    float mean, count;
+    crit::ce_mean(part, nblocks, &mean, &count);
     if (threadIdx.x == 0) {
-        float sa = 0.f, sb = 0.f;
-        for (int w = 0; w < kThreads / 64; ++w) {
-            sa += red[0][w];
-            sb += red[1][w];
-        }
-        out[0] = sb > 0.f ? sa / sb : 0.f;
-        out[1] = sb;
+        out[0] = mean;
+        out[1] = count;
     }
 }
 
@@ -95,10 +59,7 @@ __global__ __launch_bounds__(kThreads) void ce_bwd_kernel(const float* __restric
     for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
         const int64_t r = e / c;
         const int j = (int)(e - r * c);
-        const float l = lse[r];
-        float g = 0.f;
-        if (l != INFINITY) g = (expf(x[e] - l) - (j == label[r] ? 1.f : 0.f)) * scale;
-        dx[e] = g;
+        dx[e] = crit::ce_grad(x[e], lse[r], j == label[r], scale);
     }
 }
 

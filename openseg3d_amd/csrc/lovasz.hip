@@ -19,25 +19,14 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.hpp"
+#include "criterion_device.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kItems = 8;
-constexpr int kChunk = kThreads * kItems;  // 2048 sorted elements per workgroup
-constexpr int kMaxClasses = 64;
-
-// softmax(row)[j] == expf(row[j] - m) / s; the row is re-read from L1 instead of being held in a runtime-indexed
-// register array (which the compiler would put in scratch)
-__device__ __forceinline__ void softmax_stats(const float* __restrict__ row, int c, float* m_out, float* s_out) {
-    float m = row[0];
-    for (int j = 1; j < c; ++j) m = fmaxf(m, row[j]);
-    float s = 0.f;
-    for (int j = 0; j < c; ++j) s += expf(row[j] - m);
-    *m_out = m;
-    *s_out = s;
-}
+using crit::class_bits;
+using crit::kChunk;
+using crit::kMaxClasses;
+using crit::kThreads;
 
 __global__ __launch_bounds__(kThreads) void lovasz_keys(const float* __restrict__ x, const int64_t* __restrict__ label,
                                                         int n, int c, int64_t ignore_index,
@@ -46,14 +35,13 @@ __global__ __launch_bounds__(kThreads) void lovasz_keys(const float* __restrict_
     if (r >= n) return;
     const float* row = x + (int64_t)r * c;
     float m, s;
-    softmax_stats(row, c, &m, &s);
+    crit::softmax_stats(row, c, &m, &s);
     const int64_t y = label[r];
     const bool valid = y != ignore_index;
     for (int j = 0; j < c; ++j) {
         const bool fg = valid && y == j;
-        const float err = valid ? fabsf((fg ? 1.f : 0.f) - expf(row[j] - m) / s) : 0.f;
         const int64_t at = (int64_t)j * n + r;
-        keys[at] = ((unsigned long long)j << 32) | __float_as_uint(err);
+        keys[at] = ((unsigned long long)j << 32) | crit::lovasz_err_bits(row, j, m, s, valid, fg);
         vals[at] = (uint32_t)r | (fg ? 0x80000000u : 0u);
     }
 }
@@ -61,39 +49,16 @@ __global__ __launch_bounds__(kThreads) void lovasz_keys(const float* __restrict_
 __global__ __launch_bounds__(kThreads) void lovasz_count(const uint32_t* __restrict__ vals, int n, int nchunks,
                                                          int* __restrict__ chunk_cnt /*[c][nchunks]*/) {
     const int seg = blockIdx.y, chunk = blockIdx.x;
-    const uint32_t* v = vals + (int64_t)seg * n;
-    int cnt = 0;
-    const int base = chunk * kChunk + threadIdx.x * kItems;
-    for (int j = 0; j < kItems; ++j)
-        if (base + j < n) cnt += (int)(v[base + j] >> 31);
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, SEG3D_WAVE);
-    __shared__ int red[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < kThreads / 64; ++w) t += red[w];
-        chunk_cnt[seg * nchunks + chunk] = t;
-    }
+    const int t = crit::lovasz_chunk_count(vals + (int64_t)seg * n, n, chunk);
+    if (threadIdx.x == 0) chunk_cnt[seg * nchunks + chunk] = t;
 }
 
 // one wave per sorted segment: exclusive scan of its chunk counts, total foreground count
 __global__ __launch_bounds__(64) void lovasz_offsets(const int* __restrict__ chunk_cnt, int nchunks,
                                                      int* __restrict__ chunk_off, int* __restrict__ total) {
-    const int seg = blockIdx.x, lane = threadIdx.x;
-    int carry = 0;
-    for (int t0 = 0; t0 < nchunks; t0 += 64) {
-        const int i = t0 + lane;
-        const int v = i < nchunks ? chunk_cnt[seg * nchunks + i] : 0;
-        int inc = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off, SEG3D_WAVE);
-            if (lane >= off) inc += o;
-        }
-        if (i < nchunks) chunk_off[seg * nchunks + i] = carry + inc - v;
-        carry += __shfl(inc, 63, SEG3D_WAVE);
-    }
-    if (lane == 0) total[seg] = carry;
+    const int seg = blockIdx.x;
+    const int t = crit::lovasz_segment_offsets(chunk_cnt + seg * nchunks, nchunks, chunk_off + seg * nchunks);
+    if (threadIdx.x == 0) total[seg] = t;
 }
 
 __global__ __launch_bounds__(kThreads) void lovasz_grad(const unsigned long long* __restrict__ keys,
@@ -104,55 +69,9 @@ __global__ __launch_bounds__(kThreads) void lovasz_grad(const unsigned long long
     const int seg = blockIdx.y, chunk = blockIdx.x;
     const int cls = c - 1 - seg;  // descending sort on the class bits
     const int64_t seg0 = (int64_t)seg * n;
-    const int base = chunk * kChunk + threadIdx.x * kItems;
-    uint32_t v[kItems];
-    float err[kItems];
-    int mine = 0;
-    for (int j = 0; j < kItems; ++j) {
-        const bool in = base + j < n;
-        v[j] = in ? vals[seg0 + base + j] : 0u;
-        err[j] = in ? __uint_as_float((uint32_t)keys[seg0 + base + j]) : 0.f;
-        mine += (int)(v[j] >> 31);
-    }
-    // exclusive scan of the per-thread foreground counts over the workgroup
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = mine;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, SEG3D_WAVE);
-        if (lane >= off) inc += o;
-    }
-    __shared__ int wsum[kThreads / 64];
-    __shared__ float wdot[kThreads / 64];
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int before = chunk_off[seg * nchunks + chunk] + inc - mine;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-
-    const float gts = (float)total[seg];
-    float dot = 0.f;
-    int cum = before;
-    for (int j = 0; j < kItems; ++j) {
-        const int k = base + j;
-        if (k >= n) break;
-        const int fg = (int)(v[j] >> 31);
-        const int cum_prev = cum;
-        cum += fg;
-        // lovasz_grad, lovasz_loss.py:17-25: jaccard = 1 - (gts - cumsum(gt)) / (gts + cumsum(1 - gt)), then differences
-        float g = 1.f - (gts - (float)cum) / (gts + (float)(k + 1 - cum));
-        if (k > 0) g -= 1.f - (gts - (float)cum_prev) / (gts + (float)(k - cum_prev));
-        dot += err[j] * g;
-        // d|fg - p| / dp: -1 on foreground rows, +1 on background rows, 0 where the error is exactly 0 (torch abs')
-        const float sgn = err[j] == 0.f ? 0.f : (fg ? -1.f : 1.f);
-        coef[(int64_t)(v[j] & 0x7FFFFFFFu) * c + cls] = sgn * g;
-    }
-    for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off, SEG3D_WAVE);
-    if (lane == 0) wdot[wave] = dot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < kThreads / 64; ++w) t += wdot[w];
-        part[seg * nchunks + chunk] = t;
-    }
+    const float t = crit::lovasz_chunk_grad(keys + seg0, vals + seg0, 0xFFFFFFFFu, n, c, cls, chunk,
+                                            chunk_off[seg * nchunks + chunk], total[seg], coef);
+    if (threadIdx.x == 0) part[seg * nchunks + chunk] = t;
 }
 
 // stats[0] = loss, stats[1] = number of classes averaged, stats[2 + cls] = d loss / d loss_cls
@@ -161,32 +80,7 @@ __global__ __launch_bounds__(kMaxClasses) void lovasz_finalize(const float* __re
                                                                const int32_t* __restrict__ include,
                                                                const float* __restrict__ class_weight,
                                                                float* __restrict__ stats) {
-    __shared__ float loss_c[kMaxClasses];
-    __shared__ float w_c[kMaxClasses];
-    const int cls = threadIdx.x;
-    if (cls < c) {
-        const int seg = c - 1 - cls;
-        float s = 0.f;
-        for (int i = 0; i < nchunks; ++i) s += part[seg * nchunks + i];
-        bool use = mode == 0 ? total[seg] > 0 : true;  // 'present' (lovasz_loss.py:143-144) | 'all'
-        if (include) use = include[cls] != 0;          // explicit class list: no presence test (lovasz_loss.py:140)
-        const float w = use ? (class_weight ? class_weight[cls] : 1.f) : 0.f;
-        loss_c[cls] = use ? s * w : 0.f;
-        w_c[cls] = use ? w : -1.f;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sum = 0.f;
-        int used = 0;
-        for (int j = 0; j < c; ++j)
-            if (w_c[j] >= 0.f) {
-                sum += loss_c[j];
-                ++used;
-            }
-        stats[0] = used ? sum / (float)used : 0.f;
-        stats[1] = (float)used;
-        for (int j = 0; j < c; ++j) stats[2 + j] = (w_c[j] >= 0.f && used) ? w_c[j] / (float)used : 0.f;
-    }
+    crit::lovasz_head_finalize(part, total, c, nchunks, mode, include, class_weight, stats);
 }
 
 __global__ __launch_bounds__(kThreads) void lovasz_bwd(const float* __restrict__ x, const float* __restrict__ coef,
@@ -196,22 +90,15 @@ __global__ __launch_bounds__(kThreads) void lovasz_bwd(const float* __restrict__
     if (r >= n) return;
     const float* row = x + (int64_t)r * c;
     float m, s;
-    softmax_stats(row, c, &m, &s);
+    crit::softmax_stats(row, c, &m, &s);
     const float g = gout[0];
     const float* cf = coef + (int64_t)r * c;
-    float dot = 0.f;
-    for (int j = 0; j < c; ++j) dot += expf(row[j] - m) / s * (cf[j] * stats[2 + j] * g);
+    const float dot = crit::lovasz_row_dot(row, cf, stats + 2, c, m, s, g);
     float* out = dx + (int64_t)r * c;
-    for (int j = 0; j < c; ++j) out[j] = expf(row[j] - m) / s * (cf[j] * stats[2 + j] * g - dot);
+    for (int j = 0; j < c; ++j) out[j] = crit::lovasz_grad_elem(row[j], cf[j], stats[2 + j], m, s, g, dot);
 }
 
 using Key = unsigned long long;
-
-int class_bits(int c) {
-    int b = 0;
-    while ((1 << b) < c) ++b;
-    return b;
-}
 
 struct Plan {
     int64_t total;

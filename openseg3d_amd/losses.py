@@ -9,7 +9,8 @@
 
 Same class names, constructor arguments and ``loss_name`` properties.  The configurations build_criterion can produce
 (OHEM by probability threshold, multi-class Lovasz over the whole batch) run in libseg3d_hip.so: one pass each way for
-the cross-entropy terms, one device sort for all classes of the Lovasz term.  Options the builder never sets (OHEM by
+the cross-entropy terms, one device sort for all classes of the Lovasz term -- and compute_loss, given such a list, makes one
+call for all heads and both terms (ops.fused_criterion, same bits).  Options the builder never sets (OHEM by
 keep_ratio, per-image / binary Lovasz) are composed from torch ops on the same device tensors.  FocalLoss and DiceLoss,
 which no configuration of the reference builds but its package exports, run in the library too on CUDA float32 inputs
 (build_criterion keys 'focal' and 'dice', beyond the reference's three); other inputs take a torch composition of the
@@ -265,24 +266,77 @@ def build_criterion(cfg, dataset):
 
 
 AUX_OVERLAP = os.environ.get("SEG3D_AUX_OVERLAP", "1") != "0"
+# all heads and both terms in one native call (ops.fused_criterion) where the criterion list allows it; 0 = the loop below
+FUSED_CRITERION = os.environ.get("SEG3D_CRITERION_FUSED", "1") != "0"
+
+
+def _fused_terms(criterion):
+    """(ignore_index, keep_thresh, ce weight, lovasz weight) when the list is what build_criterion makes from one of 'ce' /
+    'ohem_ce' (by keep_thresh), then 'lovasz' (multi-class, whole batch, classes 'present', no class weights), or one of
+    the two alone; None for any other list (focal, dice, class weights, OHEM by ratio, another order)."""
+    ce = lov = None
+    for fn, w in criterion:
+        if lov is None and ce is None and type(fn) is CrossEntropyLoss:
+            ce = (fn.ignore_index, None, w)
+        elif (lov is None and ce is None and type(fn) is OHEMCrossEntropyLoss and fn.class_weight is None
+              and not fn.keep_ratio):
+            ce = (fn.ignore_index, fn.keep_thresh, w)
+        elif (lov is None and type(fn) is LovaszLoss and fn.loss_type == "multi_class" and not fn.per_image
+              and fn.classes == "present" and fn.class_weight is None and fn.loss_weight == 1.0):
+            lov = (fn.ignore_index, w)
+        else:
+            return None
+    if ce is None and lov is None:
+        return None
+    if ce is not None and lov is not None and ce[0] != lov[0]:
+        return None
+    weights = [t[-1] for t in (ce, lov) if t is not None]
+    if not all(isinstance(w, (int, float)) for w in weights):
+        return None
+    return (ce[0] if ce is not None else lov[0], ce[1] if ce is not None else None,
+            ce[2] if ce is not None else None, lov[1] if lov is not None else None)
 
 
 def compute_loss(pred_result, data_dict, criterion, cfg):
     """tools/train.py:71-110: criterion on the point logits, the voxel logits and (x MODEL.AUX_LOSS_WEIGHT) the
     stride-8 auxiliary logits, whose ground truth is looked up by nearest fine voxel centre (ops.aux_voxel_labels)."""
-    # The auxiliary labels (a kNN lookup: no gradient, independent of the other two heads) are looked up on the second
+    # The auxiliary labels (a kNN lookup: no gradient, independent of the other two heads) come from the planned index
+    # of the batch (Segformer.prepare_batch) where there is one: a gather.  Otherwise they are looked up on the second
     # stream while this one computes the point and voxel losses; the streams meet in front of the auxiliary loss.
     aux_gt = side = None
     if "aux_voxel_out" in pred_result:
         dev = pred_result["aux_voxel_out"].device
-        overlap = AUX_OVERLAP and dev.type == "cuda"
+        planned = (pred_result.get("index_plan") or {}).get("aux_label_index")  # Segformer.forward of a planned batch
+        overlap = AUX_OVERLAP and dev.type == "cuda" and planned is None
         if overlap:
             main, side = torch.cuda.current_stream(dev), ops.side_stream(dev)
             side.wait_stream(main)
         with torch.no_grad(), torch.cuda.stream(side) if overlap else contextlib.nullcontext():
             aux_gt = ops.aux_voxel_labels(pred_result["voxel_coords"], pred_result["aux_voxel_coords"],
                                           data_dict["voxel_labels"], data_dict["batch_size"], cfg.DATASET.VOXEL_SIZE,
-                                          cfg.DATASET.POINT_CLOUD_RANGE)
+                                          cfg.DATASET.POINT_CLOUD_RANGE, index=planned)
+    heads = [(pred_result["point_out"], data_dict["point_labels"], 1.0)]
+    if "voxel_out" in pred_result:
+        heads.append((pred_result["voxel_out"], data_dict["voxel_labels"], 1.0))
+    if aux_gt is not None:
+        heads.append((pred_result["aux_voxel_out"], aux_gt, cfg.MODEL.AUX_LOSS_WEIGHT))
+    terms = _fused_terms(criterion) if FUSED_CRITERION else None
+    if (terms is not None and all(ops._loss_args_ok(x, y, 64) and x.shape[1] == heads[0][0].shape[1] for x, y, _ in heads)
+            and sum(x.numel() for x, _, _ in heads) < 1 << 31):
+        def fused(hs):
+            return ops.fused_criterion([h[0] for h in hs], [h[1] for h in hs], [h[2] for h in hs], ignore_index=terms[0],
+                                       keep_thresh=terms[1], ce_weight=terms[2], lovasz_weight=terms[3])
+
+        if side is None:
+            return fused(heads)
+        # no planned index: the lookup is under way on the second stream.  The heads in front go through one fused call
+        # beside it; the auxiliary head follows through the per-term entries once the streams have met -- the same
+        # sequence of float32 additions as one call over all heads (a call returns the running sum from 0)
+        loss = fused(heads[:-1])
+        main.wait_stream(side)
+        for fn, w in criterion:
+            loss = loss + cfg.MODEL.AUX_LOSS_WEIGHT * fn(pred_result["aux_voxel_out"], aux_gt) * w
+        return loss
     loss = 0
     for fn, w in criterion:
         loss = loss + fn(pred_result["point_out"], data_dict["point_labels"]) * w

@@ -2260,21 +2260,31 @@ def _sample_offsets_nosync(batch_col, batch_size):
     return (batch_col.view(-1, 1) == ids.view(1, -1)).sum(dim=0).cumsum(0).to(torch.int32)
 
 
-def aux_voxel_labels(voxel_coords, aux_voxel_coords, voxel_labels, batch_size, voxel_size, point_cloud_range,
-                     aux_scale=8.0):
-    """Ground truth of the auxiliary (stride-8) voxel head as tools/train.py:86-104 builds it: every coarse voxel takes
-    the label of the nearest fine voxel centre of its sample (knn_query with k = 1).  coords: [M, 4] (b, z, y, x).
+def aux_voxel_label_index(voxel_coords, aux_voxel_coords, batch_size, voxel_size, point_cloud_range, aux_scale=8.0):
+    """int64 [M_aux]: for every coarse (stride-8) voxel the row of the nearest fine voxel centre of its sample (knn_query
+    with k = 1), the index tools/train.py:86-104 gathers the auxiliary ground truth with.  coords: [M, 4] (b, z, y, x).
+    It depends on the voxel coordinates alone, so it is part of the index plan (Segformer.prepare_batch).
     The per-sample counts come from one compare-and-sum instead of a Python loop of host syncs."""
     centers = get_voxel_centers(voxel_coords[:, 1:], 1.0, voxel_size, point_cloud_range).contiguous()
     aux_centers = get_voxel_centers(aux_voxel_coords[:, 1:], aux_scale, voxel_size, point_cloud_range).contiguous()
-    off = _sample_offsets_nosync(voxel_coords[:, 0], batch_size)  # nothing in this function waits for the GPU: it
-    aux_off = _sample_offsets_nosync(aux_voxel_coords[:, 0], batch_size)  # runs between forward and backward
+    off = _sample_offsets_nosync(voxel_coords[:, 0], batch_size)  # nothing in this function waits for the GPU: without a
+    aux_off = _sample_offsets_nosync(aux_voxel_coords[:, 0], batch_size)  # plan it runs between forward and backward
     # grid for this lookup: one fine voxel per finest cell, one coarse voxel per middle cell (every coarse site has a
     # fine voxel within ~2 coarse pitches: measured 0.96 ms vs 2.45 ms with the point-cloud default on the headline
     # scene); the third level only guards against a whole-segment scan on unusual inputs
     pitch = float(max(voxel_size))
     idx, _ = knn_query(1, centers, aux_centers, off, aux_off, levels=((pitch, 0), (8 * pitch, 3), (64 * pitch, 2)))
-    return voxel_labels[idx.reshape(-1).long()]
+    return idx.reshape(-1).long()
+
+
+def aux_voxel_labels(voxel_coords, aux_voxel_coords, voxel_labels, batch_size, voxel_size, point_cloud_range,
+                     aux_scale=8.0, index=None):
+    """Ground truth of the auxiliary (stride-8) voxel head as tools/train.py:86-104 builds it: every coarse voxel takes
+    the label of the nearest fine voxel centre of its sample.  ``index``: a planned aux_voxel_label_index of the same
+    coordinates; only the gather is left then."""
+    if index is None:
+        index = aux_voxel_label_index(voxel_coords, aux_voxel_coords, batch_size, voxel_size, point_cloud_range, aux_scale)
+    return voxel_labels[index]
 
 
 # ------------------------------------------------------------------------------------------ SURVEY 8(f): loss
@@ -2466,6 +2476,90 @@ def lovasz_softmax(logits, labels, ignore_index=255, classes="present", class_we
     if class_weight is not None:
         class_weight = _f32c(torch.as_tensor(class_weight, dtype=torch.float32, device=logits.device))
     return _LovaszSoftmaxFn.apply(logits, labels, ignore_index, mode, include, class_weight)
+
+
+CRITERION_MAX_HEADS = 4
+CRITERION_CE, CRITERION_LOVASZ = 1, 2
+_CRITERION_STATS_STRIDE = 68
+
+
+class CriterionHead(ctypes.Structure):
+    _fields_ = [("logits", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("n", ctypes.c_int64), ("weight", ctypes.c_float)]
+
+
+class CriterionTable(ctypes.Structure):
+    """seg3d_criterion_table (include/seg3d_hip.h): up to four heads {logits, labels, n, head weight}."""
+    _fields_ = [("n_heads", ctypes.c_int32), ("heads", CriterionHead * CRITERION_MAX_HEADS)]
+
+
+def criterion_table(logits, labels, head_weights):
+    tab = CriterionTable()
+    tab.n_heads = len(logits)
+    for i, (x, y, w) in enumerate(zip(logits, labels, head_weights)):
+        tab.heads[i].logits, tab.heads[i].labels = x.data_ptr() or None, y.data_ptr() or None
+        tab.heads[i].n, tab.heads[i].weight = x.shape[0], float(w)
+    return tab
+
+
+class _CriterionFn(torch.autograd.Function):
+    """All heads and both terms of the training criterion in one call (seg3d_criterion_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, args, *tensors):
+        head_weights, terms, ignore_index, keep_thresh, w_ce, w_lovasz = args
+        nh = len(tensors) // 2
+        xs = [_f32c(t) for t in tensors[:nh]]
+        labs = [t.contiguous() for t in tensors[nh:]]
+        dev, c = xs[0].device, xs[0].shape[1]
+        rows = sum(x.shape[0] for x in xs)
+        lse = torch.empty((rows if terms & CRITERION_CE else 0,), dtype=torch.float32, device=dev)
+        coef = torch.empty((rows if terms & CRITERION_LOVASZ else 0, c), dtype=torch.float32, device=dev)
+        stats = torch.empty((nh, _CRITERION_STATS_STRIDE), dtype=torch.float32, device=dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        tab = criterion_table(xs, labs, head_weights)
+        ws_bytes = _lib.query("seg3d_criterion_workspace_bytes", ctypes.byref(tab), c, terms)
+        if ws_bytes == 0:
+            raise _lib.Seg3dError("seg3d_criterion_workspace_bytes = 0: 1..4 heads, c <= 64, sum n * c below 2^31")
+        ws = _workspace(ws_bytes, dev)
+        _lib.call("seg3d_criterion_fwd", ctypes.byref(tab), c, terms, int(ignore_index), float(keep_thresh), float(w_ce),
+                  float(w_lovasz), _ptr(lse), _ptr(coef), _ptr(stats), _ptr(loss), _ptr(ws), ws_bytes, _stream())
+        ctx.save_for_backward(lse, coef, stats, *xs, *labs)
+        ctx.args = (tuple(float(w) for w in head_weights), terms, float(w_ce), float(w_lovasz))
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lse, coef, stats = ctx.saved_tensors[:3]
+        rest = ctx.saved_tensors[3:]
+        nh = len(rest) // 2
+        xs, labs = rest[:nh], rest[nh:]
+        head_weights, terms, w_ce, w_lovasz = ctx.args
+        dxs = [torch.empty_like(x) for x in xs]
+        gg = _f32c(g.reshape(1))
+        tab = criterion_table(xs, labs, head_weights)
+        out = (ctypes.c_void_p * CRITERION_MAX_HEADS)(*[d.data_ptr() or None for d in dxs])
+        _lib.call("seg3d_criterion_bwd", ctypes.byref(tab), xs[0].shape[1], terms, w_ce, w_lovasz, _ptr(lse), _ptr(coef),
+                  _ptr(stats), _ptr(gg), out, _stream())
+        return (None, *dxs, *([None] * nh))
+
+
+def fused_criterion(logits, labels, head_weights, ignore_index=255, keep_thresh=None, ce_weight=None, lovasz_weight=None):
+    """The criterion of tools/train.py:71-110 over up to four heads in one native call: per head (in the order given)
+    ``(head_weight * cross_entropy(...)) * ce_weight`` then ``(head_weight * lovasz_softmax(...)) * lovasz_weight``, added
+    up in float32 from 0.  A term whose weight is None is left out.  Loss and logit gradients carry the bits of the sums
+    of ``ops.cross_entropy`` (with ``keep_thresh``) and ``ops.lovasz_softmax`` ('present', no class weights).
+    logits: float32 [n_h, C <= 64] with one C; labels: int64 [n_h]."""
+    logits, labels = list(logits), list(labels)
+    if not 1 <= len(logits) <= CRITERION_MAX_HEADS or len(labels) != len(logits) or len(head_weights) != len(logits):
+        raise ValueError("fused_criterion: one to four heads, one label tensor and one weight per head")
+    if any(not _loss_args_ok(x, y, 64) or x.shape[1] != logits[0].shape[1] for x, y in zip(logits, labels)):
+        raise ValueError("fused_criterion: float32 [n, C <= 64] logits of one width and int64 [n] labels on the GPU")
+    terms = (CRITERION_CE if ce_weight is not None else 0) | (CRITERION_LOVASZ if lovasz_weight is not None else 0)
+    if not terms:
+        raise ValueError("fused_criterion: at least one of ce_weight and lovasz_weight")
+    args = (tuple(head_weights), terms, ignore_index, keep_thresh if keep_thresh else 0.0,
+            ce_weight if ce_weight is not None else 0.0, lovasz_weight if lovasz_weight is not None else 0.0)
+    return _CriterionFn.apply(args, *logits, *labels)
 
 
 # ------------------------------------------------------------------------------------------ evaluation (csrc/eval.hip)

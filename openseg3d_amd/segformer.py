@@ -388,7 +388,22 @@ class Segformer(nn.Module):
             # DeepFusionBlock's neighbour search reads the points only (13 ms of a 63 ms multi-sweep forward): part of the plan
             cur_points, _ = self._current_sweep(batch_dict)
             batch_dict["fusion_knn"] = self.deep_fusion.neighbours(cur_points, batch_dict["point_id_offset"].int())
+        if self.training and "aux_label_index" not in batch_dict:
+            # the auxiliary head's ground truth is gathered through the nearest fine voxel of every stride-8 site
+            # (losses.compute_loss): coordinates only, so the search belongs here and not between forward and backward
+            # (training only: an inference pipeline has no criterion to feed)
+            batch_dict["aux_label_index"] = self._aux_label_index(batch_dict)
         return batch_dict
+
+    def _aux_label_index(self, batch_dict):
+        """ops.aux_voxel_label_index between the plan's finest and stride-8 site lists (the coordinates the forward returns
+        as voxel_coords / aux_voxel_coords)."""
+        fine = coarse = batch_dict["site_level"]
+        for _ in range(3):
+            coarse = coarse.down()[0]
+        pt = self.point_transformer
+        return ops.aux_voxel_label_index(fine.coords, coarse.coords, batch_dict["batch_size"], pt.voxel_size,
+                                         pt.point_cloud_range)
 
     def _current_sweep(self, batch_dict):
         """(rows of the current sweep without the batch column, their row numbers or None) -- segformer.py:96-100; the row
@@ -465,6 +480,11 @@ class Segformer(nn.Module):
         result["aux_voxel_out"] = batch_dict["aux_voxel_out"]
         result["voxel_coords"] = batch_dict["voxel_coords"]
         result["aux_voxel_coords"] = batch_dict["aux_voxel_coords"]
+        if "aux_label_index" in batch_dict:
+            # planned by prepare_batch: compute_loss gathers the aux labels through it.  An entry, so that copies of the
+            # result and the data-parallel wrappers (which rebuild it entry by entry) keep it; a dict of its own, because
+            # it is plan material and not one of the forward's output tensors
+            result["index_plan"] = {"aux_label_index": batch_dict["aux_label_index"]}
         return result
 
 
