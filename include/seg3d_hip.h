@@ -735,6 +735,67 @@ int seg3d_knn_interpolate_bwd_host(const float* dout, const float* weight, const
                                    const int32_t* pair_offsets, int64_t n, int64_t m, int32_t k, int32_t c,
                                    float* dfeat);
 
+/* ------------------------------------------------------------------------------------------
+ * One-output-channel submanifold convolution with an optional fused sigmoid gate (csrc/sa_gate.hip) -- SALayer,
+ * seg3d/models/layers/sa_layer.py:8-25: SubMConv3d(planes, 1, 3, padding=1, bias=False) -> sigmoid -> x * gate; without
+ * the gate, the plain C -> 1 conv that the MFMA paths (out_channels % 16 == 0) do not cover.
+ *   x    float32 [M, C] contiguous          nbr  int32 [27][M], -1 = inactive, as seg3d_rulebook_subm writes it
+ *   w    float32 [27, C] = weight[0] of a [1, 3, 3, 3, C] parameter viewed flat, same offset index k as the table
+ *   bias DEVICE pointer (host pointer for the _host twins) to one float, or NULL
+ *   C % 4 == 0, 4 <= C <= 1024, 0 <= M < 2^31 - 1; anything else is SEG3D_EINVAL.  M = 0: OK, nothing is written (the
+ *   backward still writes dw = 0 and dbias = 0 when asked for them).
+ *   ALIGNMENT: x, w, y_out (forward) and dy, x (seg3d_subm_dot_bwd_ds) are read and written as 16-byte vectors and must
+ *   be 16-byte aligned: a pointer that is not is SEG3D_EINVAL, nothing is launched.  seg3d_subm_dot_bwd has no
+ *   requirement beyond float alignment.
+ *   THE TABLE MUST BE A SUBMANIFOLD TABLE: nbr[13][i] == i, and nbr[k][i] == j exactly when nbr[26 - k][j] == i.  The
+ *   backward RELIES on this mirror property (it is what lets it gather scalars instead of rows) and does not check it;
+ *   with any other table its gradients are not the gradients of the forward.  An entry outside [0, M) is treated as -1
+ *   and never used as an address.
+ * Math:  s_i = bias + sum_k [nbr[k][i] >= 0] dot(x[nbr[k][i]], w[k]);  g_i = sigmoid(s_i);  y_i = x_i g_i
+ *   sigmoid(s): e = expf(-|s|), then 1 / (1 + e) for s >= 0 and e / (1 + e) for s < 0 -- expf never overflows, no NaN for
+ *   any finite s; g is exactly 1 from s >= 17 on (1 + e rounds to 1) and exactly 0 from s <= -104 on (expf underflows to
+ *   0; between -87.4 and -104 it is the denormal the exact sigmoid rounds to).
+ * Backward, given dy:  dg_i = dot(dy_i, x_i);  ds_i = (dg_i g_i) (1 - g_i)   [seg3d_subm_dot_bwd_ds; g from s again]
+ *   dx_j = dy_j g_j + sum_k [nbr[k][j] >= 0] ds[nbr[k][j]] w[26 - k]
+ *   dw[k] = sum_j [nbr[26 - k][j] >= 0] ds[nbr[26 - k][j]] x_j;   dbias = sum_j ds_j
+ *   -- 27 scalars of ds per row, x and dy streamed once, no second gather of feature rows.
+ * seg3d_subm_dot_fwd: one launch; writes s [M]; with y_out != NULL also y [M, C] (the fused layer).
+ * seg3d_subm_dot_bwd_ds: ds [M] from dy, x, s.  The plain conv has ds = dout and skips it.
+ * seg3d_subm_dot_bwd: dy == NULL is the plain conv (no dy g term; s is not read).  dx, dw, dbias: NULL = not wanted, not
+ *   computed (dx == NULL: dy, w not read; dw == dbias == NULL: x not read, no scratch needed).  scratch:
+ *   seg3d_subm_dot_scratch_bytes(M, C) bytes for the per-block partial weight gradients, else SEG3D_EWORKSPACE.
+ * ORDER OF SUMMATION (part of the contract; every product and every sum is rounded to float32 on its own, no fused
+ * multiply-add; no float atomics; the _host twins -- plain C++, host pointers, no HIP call -- use the same order and
+ * return the same bits wherever no expf is involved, i.e. s, and dx / dw / dbias of the plain conv):
+ *   channel reduction (s and dg).  The row is cut into groups of 4 consecutive floats, group c4 = channels 4 c4 .. 4 c4 + 3.
+ *     p(c4, k) = ((a0 b0 + a1 b1) + a2 b2) + a3 b3, in component order.  Per group the neighbours are summed in ascending
+ *     k from 0: A(c4) = ((0 + p(c4, k1)) + p(c4, k2)) + ... over the offsets present.  With L = the power of two >= C / 4,
+ *     at most 64, lane l of L sums its groups c4 = l, l + L, l + 2L, ... (< C / 4) in ascending order starting from the
+ *     first, Q(l) = (A(l) + A(l + L)) + ...; a lane without a group has Q = 0.  Then the fixed tree
+ *     for off = L / 2, L / 4, ..., 1: Q(l) = Q(l) + Q(l + off) for l < off;  the row's sum is Q(0), and s = Q(0) + bias (no
+ *     addition without a bias).  The shape depends on C alone, not on M or on the launch.
+ *   backward.  d(k, j) = ds[nbr[k][j]], and 0 where row j has no neighbour at offset k: such an offset is not skipped,
+ *     its products (+-0) are added like any other (the loop has no branch).
+ *   dx.  T = ((0 + d(0, j) w[26]) + d(1, j) w[25]) + ... + d(26, j) w[0], per channel; dx = dy g + T, or T alone for the
+ *     plain conv.
+ *   dw, dbias.  Rows are cut into blocks of SEG3D_SUBM_DOT_ROWS consecutive rows.  Per block every (k, c) is summed from
+ *     0 over the block's rows j in ascending order, dw[26 - k][c] += d(k, j) x[j][c], and so is ds for dbias; the block
+ *     partials are then added from 0 left to right: ((0 + block 0) + block 1) + ... */
+#define SEG3D_SUBM_DOT_ROWS 128
+size_t seg3d_subm_dot_scratch_bytes(int64_t M, int32_t C);
+int seg3d_subm_dot_fwd(const float* x, const int32_t* nbr, const float* w, const float* bias, int64_t M, int32_t C,
+                       float* s_out, float* y_out, void* stream);
+int seg3d_subm_dot_fwd_host(const float* x, const int32_t* nbr, const float* w, const float* bias, int64_t M, int32_t C,
+                            float* s_out, float* y_out);
+int seg3d_subm_dot_bwd_ds(const float* dy, const float* x, const float* s, int64_t M, int32_t C, float* ds_out,
+                          void* stream);
+int seg3d_subm_dot_bwd_ds_host(const float* dy, const float* x, const float* s, int64_t M, int32_t C, float* ds_out);
+int seg3d_subm_dot_bwd(const float* dy, const float* x, const float* s, const float* ds, const int32_t* nbr,
+                       const float* w, int64_t M, int32_t C, float* dx, float* dw, float* dbias, void* scratch,
+                       size_t scratch_bytes, void* stream);
+int seg3d_subm_dot_bwd_host(const float* dy, const float* x, const float* s, const float* ds, const int32_t* nbr,
+                            const float* w, int64_t M, int32_t C, float* dx, float* dw, float* dbias);
+
 /*
  * SURVEY 8(f) rank 2  WaymoDataset.prepare_voxel_labels (seg3d/datasets/waymo_dataset.py:213-246): label of a voxel =
  * most frequent label (uint8, 0..255, the ignore label counted like any other) among its points, ties to the smallest

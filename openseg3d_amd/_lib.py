@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 51
+ABI_VERSION = 52
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -143,7 +143,14 @@ SIGNATURES = {
     "seg3d_knn_interpolate_fwd_host": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _i32, _p, _p]),
     "seg3d_knn_interpolate_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _p, _p, _sz, _p]),
     "seg3d_knn_interpolate_bwd_host": (ctypes.c_int, [_p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _p]),
-    "seg3d_gather_rows": (ctypes.c_int, [_p, _p, _i64, _i32, _p, _p]),
+    "seg3d_subm_dot_scratch_bytes": (_sz, [_i64, _i32]),
+    "seg3d_subm_dot_fwd": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p, _p]),
+    "seg3d_subm_dot_fwd_host": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _p, _p]),
+    "seg3d_subm_dot_bwd_ds": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p, _p]),
+    "seg3d_subm_dot_bwd_ds_host": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _p]),
+    "seg3d_subm_dot_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, _sz, _p]),
+    "seg3d_subm_dot_bwd_host": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p]),
+    "seg3d_gather_rows":(ctypes.c_int, [_p, _p, _i64, _i32, _p, _p]),
     "seg3d_class_context_fwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f, _p, _p, _p, _p, _p]),
     "seg3d_class_context_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i64, _i32, _i32, _f, _p, _p, _p, _p]),
     "seg3d_knn_attention_fwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i32, _i32, _f, _p, _p, _p]),

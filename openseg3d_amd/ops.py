@@ -10,6 +10,8 @@ The names exported for reference compatibility mirror ``seg3d.ops`` (seg3d/ops/_
 vfe.py:25 and se_layer.py:25.  ``query_and_group`` / ``interpolation`` (seg3d/utils/pointops_utils.py:25-61) and
 ``furthestsampling`` / ``sectorized_fps`` (seg3d/ops/sampling) are mirrored too; ``query_and_group`` with a given idx,
 ``knn_interpolate`` and the two sampling calls also take CPU tensors, which run the library's host entries.
+``subm_dot`` / ``sa_gate`` (the one-channel submanifold conv and the fused SALayer, seg3d/models/layers/sa_layer.py:8-25)
+take CUDA tensors (device entries) or CPU tensors (host entries), with autograd on both.
 """
 import ctypes
 import weakref
@@ -3737,3 +3739,85 @@ def interpolation(xyz, new_xyz, feat, offset, new_offset, k=3):
                               "neighbour table for CPU tensors")
     idx, dist = knn_query(int(k), xyz, new_xyz, offset, new_offset)
     return knn_interpolate(feat, idx, dist)
+
+
+# ---------------------------------------------------------------------------------------------- SALayer (csrc/sa_gate.hip)
+def _subm_dot_args(what, x, weight, bias, nbr):
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError(f"{what}: x must be a float32 [M, C] tensor, got {tuple(getattr(x, 'shape', ()))}")
+    if x.dtype != torch.float32:
+        raise _lib.Seg3dError(f"{what}: x must be float32, got {x.dtype} (bfloat16 conv storage is not supported here)")
+    m, c = x.shape
+    if c % 4 or not 4 <= c <= 1024:
+        raise _lib.Seg3dError(f"{what}: C = {c} channels; C % 4 == 0 and 4 <= C <= 1024 are supported (SEG3D_EINVAL)")
+    if weight.dtype != torch.float32 or weight.numel() != 27 * c:
+        raise ValueError(f"{what}: weight must be float32 [1, 3, 3, 3, {c}], got {tuple(weight.shape)} {weight.dtype}")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != 1):
+        raise ValueError(f"{what}: bias must be one float32 value, got {tuple(bias.shape)} {bias.dtype}")
+    if not isinstance(nbr, torch.Tensor) or nbr.dtype != torch.int32 or tuple(nbr.shape) != (27, m):
+        raise ValueError(f"{what}: nbr must be the int32 [27, M = {m}] submanifold table (SiteLevel.subm()), got "
+                         f"{tuple(getattr(nbr, 'shape', ()))} {getattr(nbr, 'dtype', None)}")
+    kind = _pointops_kind(what, x, weight, bias, nbr)
+    if not x.is_contiguous():
+        x = x.contiguous()
+    return kind, x, nbr.contiguous()
+
+
+class _SubmDotFn(torch.autograd.Function):
+    """One-channel submanifold conv (gate=False -> s [M, 1]) or the fused SALayer (gate=True -> x * sigmoid(s) [M, C]):
+    seg3d_subm_dot_fwd / _bwd_ds / _bwd.  Saves x and the logits s; the gate is recomputed from s in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, nbr, gate, kind):
+        m, c = x.shape
+        w = weight.detach().reshape(27, c).contiguous()
+        s = torch.empty((m,), dtype=torch.float32, device=x.device)
+        y = torch.empty((m, c), dtype=torch.float32, device=x.device) if gate else None
+        _pointops_call(kind, "seg3d_subm_dot_fwd", _ptr(x), _ptr(nbr), _ptr(w), _ptr(bias), m, c, _ptr(s), _ptr(y))
+        ctx.save_for_backward(x, w, nbr, s)
+        ctx.kind, ctx.gate, ctx.wshape, ctx.has_bias = kind, gate, weight.shape, bias is not None
+        return y if gate else s.view(m, 1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w, nbr, s = ctx.saved_tensors
+        kind, gate = ctx.kind, ctx.gate
+        m, c = x.shape
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        need_b = need_b and ctx.has_bias
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None, None
+        dev = x.device
+        dout = _f32c(dout)
+        if gate:
+            if dout.data_ptr() % 16:
+                dout = dout.clone()  # the row dot reads 16-byte vectors
+            ds = torch.empty((m,), dtype=torch.float32, device=dev)
+            _pointops_call(kind, "seg3d_subm_dot_bwd_ds", _ptr(dout), _ptr(x), _ptr(s), m, c, _ptr(ds))
+        else:
+            ds = dout.reshape(m)
+        dx = torch.empty((m, c), dtype=torch.float32, device=dev) if need_x else None
+        dw = torch.empty((27, c), dtype=torch.float32, device=dev) if need_w else None
+        db = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
+        scratch = False
+        if kind == "cuda":
+            scratch = _workspace(_lib.query("seg3d_subm_dot_scratch_bytes", m, c), dev) if (need_w or need_b) else None
+        _pointops_call(kind, "seg3d_subm_dot_bwd", _ptr(dout) if gate else None, _ptr(x), _ptr(s), _ptr(ds), _ptr(nbr),
+                       _ptr(w), m, c, _ptr(dx), _ptr(dw), _ptr(db), scratch=scratch)
+        return dx, dw.view(ctx.wshape) if need_w else None, db, None, None, None
+
+
+def subm_dot(x, weight, bias, nbr):
+    """SubMConv3d(C, 1, 3, padding=1): x float32 [M, C], weight [1, 3, 3, 3, C], bias [1] or None, nbr the level's
+    submanifold table (``SiteLevel.subm()``: the backward relies on its mirror property) -> [M, 1].  Differentiable in
+    x, weight and bias (fixed-order sums, no atomics; include/seg3d_hip.h).  CUDA tensors run the device entries, CPU
+    tensors the host entries."""
+    kind, x, nbr = _subm_dot_args("subm_dot", x, weight, bias, nbr)
+    return _SubmDotFn.apply(x, weight, bias, nbr, False, kind)
+
+
+def sa_gate(x, weight, nbr):
+    """SALayer (sa_layer.py:8-25) as one op: x * sigmoid(SubMConv3d(C, 1, 3, padding=1, bias=False)(x)) -> [M, C].  One
+    forward launch; the backward keeps the logits [M], not the gate and not an [M, C] product."""
+    kind, x, nbr = _subm_dot_args("sa_gate", x, weight, None, nbr)
+    return _SubmDotFn.apply(x, weight, None, nbr, True, kind)

@@ -125,23 +125,51 @@ class FlattenSELayer(nn.Module):
         return x * self.fc(pooled)[indices]
 
 
+class SALayer(spconv.SparseModule):
+    """Spatial attention (sa_layer.py:8-25): x * sigmoid(SubMConv3d(planes, 1, 3, padding=1, bias=False)(x)) as one fused
+    op (ops.sa_gate); the parameter is ``conv.weight`` [1, 3, 3, 3, planes], as in the reference."""
+
+    def __init__(self, planes, indice_key=None):
+        super().__init__()
+        self.conv = spconv.SubMConv3d(planes, 1, 3, padding=1, bias=False, indice_key=indice_key)
+
+    def forward(self, x):
+        return x.replace_feature(ops.sa_gate(x.features, self.conv.weight, x.level.subm()))
+
+
+def _block_tail(block, y, x):
+    """bn2 (eval: folded into conv2) is done; -> se -> sa -> + identity -> ReLU (pointtransformer.py:57-66)."""
+    if block.se is not None:
+        y = y.replace_feature(block.se(y.features, y.indices[:, 0], y.level.sample_offsets()))
+    if block.sa is not None:
+        y = block.sa(y)
+    return y.replace_feature(torch.relu(y.features + x.features))
+
+
 class SparseBasicBlock(spconv.SparseModule):
-    def __init__(self, inplanes, planes, norm_fn, act_fn, indice_key=None):
+    def __init__(self, inplanes, planes, norm_fn, act_fn, indice_key=None, with_se=False, with_sa=False):
         super().__init__()
         self.conv1 = spconv.SubMConv3d(inplanes, planes, 3, padding=1, bias=True, indice_key=indice_key)
         self.bn1 = norm_fn(planes)
         self.act = act_fn
         self.conv2 = spconv.SubMConv3d(planes, planes, 3, padding=1, bias=True, indice_key=indice_key)
         self.bn2 = norm_fn(planes)
+        self.se = FlattenSELayer(planes) if with_se else None
+        self.sa = SALayer(planes, indice_key=indice_key) if with_sa else None
 
     def forward(self, x):
+        plain = self.se is None and self.sa is None
         if self.conv1.fusable_with(self.bn1, x) and self.conv2.fusable_with(self.bn2, x):  # inference: two launches
             y = self.conv1.forward_bn_act(x, self.bn1, relu=True)
-            return self.conv2.forward_bn_act(y, self.bn2, relu=True, res=x.features)
+            if plain:
+                return self.conv2.forward_bn_act(y, self.bn2, relu=True, res=x.features)
+            return _block_tail(self, self.conv2.forward_bn_act(y, self.bn2, relu=False, res=None), x)
         y = self.conv1(x)
         y = y.replace_feature(ops.batch_norm_act(y.features, self.bn1, relu=True))
         y = self.conv2(y)
-        return y.replace_feature(ops.batch_norm_act(y.features, self.bn2, relu=True, res=x.features))
+        if plain:
+            return y.replace_feature(ops.batch_norm_act(y.features, self.bn2, relu=True, res=x.features))
+        return _block_tail(self, y.replace_feature(ops.batch_norm_act(y.features, self.bn2, relu=False)), x)
 
 
 class UpBlock(spconv.SparseModule):

@@ -15,6 +15,8 @@ Design differences from spconv (MI355X-first):
     same two tables, nothing is scattered with atomics;
   * strided-conv output sites come out in ascending (b, z, y, x) order (build-defined; per-point
     logits do not depend on it).
+Output channels are a multiple of 16 (MFMA tiles), with one exception: ``SubMConv3d(Cin, 1, 3, padding=1)``, the conv of
+the reference's SALayer, runs as a gather-dot (ops.subm_dot, csrc/sa_gate.hip; Cin % 4 == 0, 4 <= Cin <= 1024).
 Parameters: ``weight`` [Cout, 3, 3, 3, Cin] (+ ``bias`` [Cout]); default init = kaiming-uniform
 (a=sqrt(5)) over fan_in = 27*Cin, bias uniform(+-1/sqrt(fan_in)), as torch's conv layers do.
 """
@@ -160,16 +162,23 @@ class SparseModule(nn.Module):
 
 
 class _Conv3x3x3(SparseModule):
+    _one_channel = False  # out_channels == 1 is accepted (SubMConv3d only: the symmetric table)
+
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=0, dilation=1, bias=True,
                  indice_key=None):
         super().__init__()
         ks = kernel_size if isinstance(kernel_size, int) else kernel_size[0]
         if ks != 3 or dilation != 1:
             raise NotImplementedError("only 3x3x3, dilation 1 is on the OpenSeg3D path")
-        if out_channels % 16:
+        # SubMConv3d(C, 1): the gather-dot of csrc/sa_gate.hip (ops.subm_dot) -- no packed weight, no tile plan, no fusion
+        self._dot = out_channels == 1 and self._one_channel
+        if self._dot and (in_channels % 4 or not 4 <= in_channels <= 1024 or stride != 1 or padding != 1):
+            raise NotImplementedError("a one-channel SubMConv3d takes padding=1, stride=1 and 4 <= in_channels <= 1024, "
+                                      "in_channels % 4 == 0")
+        if out_channels % 16 and not self._dot:
             raise NotImplementedError("output channels must be a multiple of 16 (MFMA 16x16 tiles)")
         # narrow inputs (the 6/8 raw point channels of the multi-sweep config) are zero-padded per call
-        self._pad_in = (-in_channels) % 16
+        self._pad_in = 0 if self._dot else (-in_channels) % 16
         self.in_channels, self.out_channels = in_channels, out_channels
         self.stride, self.padding, self.indice_key = stride, padding, indice_key
         self.weight = nn.Parameter(torch.empty(out_channels, 3, 3, 3, in_channels))
@@ -212,6 +221,8 @@ class _Conv3x3x3(SparseModule):
         raise NotImplementedError
 
     def forward(self, x):
+        if self._dot:
+            return x.replace_feature(ops.subm_dot(x.features, self.weight, self.bias, x.level.subm()))
         nbr, nbr_t, t_flags, order, order_t, level = self.tables(x)
         plan, plan_t = self.plans(x)
         return x.on_level(self._apply_tables(x.features, nbr, nbr_t, t_flags, order, order_t, plan, plan_t), level)
@@ -219,7 +230,7 @@ class _Conv3x3x3(SparseModule):
     def fusable_with(self, bn, x):
         """Inference only: conv -> BatchNorm(eval) -> (+ residual) -> ReLU can run as one launch."""
         return (FUSE_EVAL_BN and not torch.is_grad_enabled() and not bn.training and bn.track_running_stats and bn.affine
-                and not self._pad_in and ops.CONV_PRECISION == "bf16x3" and x.features.is_cuda
+                and not self._dot and not self._pad_in and ops.CONV_PRECISION == "bf16x3" and x.features.is_cuda
                 and (x.features.dtype == torch.float32 or (x.features.dtype == torch.bfloat16 and ops.conv_storage_bf16())))
 
     def forward_bn_act(self, x, bn, relu=True, res=None):
@@ -245,6 +256,8 @@ class _Conv3x3x3(SparseModule):
 
 
 class SubMConv3d(_Conv3x3x3):
+    _one_channel = True
+
     def tables(self, x):
         nbr = x.level.subm()
         order = x.level.mask_order()  # (the transposed table is the same table with the offsets mirrored: same grouping)

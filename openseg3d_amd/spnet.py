@@ -19,14 +19,15 @@ import torch.nn.functional as F
 from . import ops
 from . import segformer as segformer_mod
 from . import spconv
-from .segformer import (ConvBnAct, DeepFusionBlock, FlattenSELayer, FusedMLP, RowLinear, UpBlock, VFE, _bn_mlp,
-                        conv_module)
+from .segformer import (ConvBnAct, DeepFusionBlock, FlattenSELayer, FusedMLP, RowLinear, SALayer, UpBlock, VFE, _block_tail,
+                        _bn_mlp, conv_module)
 
 
 class SparseBasicBlock(spconv.SparseModule):
-    """conv-BN-ReLU-conv-BN (+ squeeze-excite over each sample's voxels) + identity, ReLU (spconv_unet.py:12-66)."""
+    """conv-BN-ReLU-conv-BN (+ squeeze-excite over each sample's voxels, + spatial attention) + identity, ReLU
+    (spconv_unet.py:12-66)."""
 
-    def __init__(self, inplanes, planes, norm_fn, act_fn, with_se=False, indice_key=None):
+    def __init__(self, inplanes, planes, norm_fn, act_fn, with_se=False, indice_key=None, with_sa=False):
         super().__init__()
         self.conv1 = spconv.SubMConv3d(inplanes, planes, 3, padding=1, bias=True, indice_key=indice_key)
         self.bn1 = norm_fn(planes)
@@ -34,9 +35,17 @@ class SparseBasicBlock(spconv.SparseModule):
         self.conv2 = spconv.SubMConv3d(planes, planes, 3, padding=1, bias=True, indice_key=indice_key)
         self.bn2 = norm_fn(planes)
         self.se = FlattenSELayer(planes) if with_se else None
-        self.sa = None  # SALayer is never enabled by the reference's SparseUnet
+        self.sa = SALayer(planes, indice_key=indice_key) if with_sa else None  # (the reference's SparseUnet never sets it)
 
     def forward(self, x):
+        if self.sa is not None:
+            if self.conv1.fusable_with(self.bn1, x) and self.conv2.fusable_with(self.bn2, x):  # inference, BatchNorm folded
+                y = self.conv1.forward_bn_act(x, self.bn1, relu=True)
+                return _block_tail(self, self.conv2.forward_bn_act(y, self.bn2, relu=False, res=None), x)
+            y = self.conv1(x)
+            y = y.replace_feature(ops.batch_norm_act(y.features, self.bn1, relu=True))
+            y = self.conv2(y)
+            return _block_tail(self, y.replace_feature(ops.batch_norm_act(y.features, self.bn2, relu=False)), x)
         if self.se is None and self.conv1.fusable_with(self.bn1, x) and self.conv2.fusable_with(self.bn2, x):
             y = self.conv1.forward_bn_act(x, self.bn1, relu=True)  # inference: BatchNorm folded, two launches
             return self.conv2.forward_bn_act(y, self.bn2, relu=True, res=x.features)
