@@ -9,9 +9,6 @@ namespace attn_fused {
 
 using namespace attn;
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 template <int DH>
 struct Cfg {
     static constexpr bool kNarrow = DH <= 12;          // several heads of one 32-query tile per workgroup
@@ -49,13 +46,6 @@ __device__ __forceinline__ float quad_sum(float x) {
 // correctly rounded sqrt + divide sequences (~40 instructions per key per tile); the operands are then rounded to
 // 16 significant bits anyway
 __device__ __forceinline__ float inv_norm(float ss) { return __builtin_amdgcn_rsqf(fmaxf(ss, kNormEps * kNormEps)); }
-
-// two fp32 -> packed bf16 hi pair and lo pair
-__device__ __forceinline__ void split2(float a, float b, uint32_t* hi, uint32_t* lo) {
-    const uint32_t w = pack_bf16(a, b);
-    *hi = w;
-    *lo = pack_bf16(a - __builtin_bit_cast(float, w << 16), b - __builtin_bit_cast(float, w & 0xFFFF0000u));
-}
 
 // Work items are dealt to the 8 XCDs in BLOCKS of consecutive items (items are sorted by window: the 32-token tiles /
 // 128-token chunks of one window are neighbours in the list and stream the SAME key / value rows, so they belong on one

@@ -21,36 +21,11 @@
 #include <atomic>
 #include <cstdlib>
 
-#include "common.hpp"
+#include "split_bf16.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-// 8 floats -> (hi, lo) bf16 fragments; hi = RNE(x), lo = RNE(x - hi)   (the arithmetic of spconv_split.hip's split8)
-__device__ __forceinline__ void split8(const f32x4& p, const f32x4& q, bf16x8* hi, bf16x8* lo) {
-    u32x4 h, l;
-    const float v[8] = {p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t ph = pack_bf16(v[2 * i], v[2 * i + 1]);
-        const float h0 = __builtin_bit_cast(float, ph << 16);
-        const float h1 = __builtin_bit_cast(float, ph & 0xFFFF0000u);
-        h[i] = ph;
-        l[i] = pack_bf16(v[2 * i] - h0, v[2 * i + 1] - h1);
-    }
-    *hi = __builtin_bit_cast(bf16x8, h);
-    *lo = __builtin_bit_cast(bf16x8, l);
-}
+using namespace sbf;
 
 // KC: 32-channel chunks of the input (ceil(cin / 32) == KC); NB: 16-column blocks of the workgroup's column block.
 // IO 0: y = x W^T + b (+ addend); IO 4: y = (x W^T) * factor (the "addend" pointer is the elementwise factor: fc2's input

@@ -22,34 +22,14 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "attn_common.hpp"
+#include "split_bf16.hpp"
 
 namespace {
 
-using namespace attn;
+using namespace sbf;
 
 constexpr int kThreads = 256;
 constexpr int kSlab = 4 * 3 * 64;  // uint4 per (32-channel step, 64-column group): [tile j][plane][lane]
-
-// 8 fp32 -> three bf16 fragments with h + m + l == x exactly (round-to-nearest at every level; |m| <= 2^-9 |x|, |l| <= 2^-18 |x|)
-__device__ __forceinline__ void split3(const float* v, bf16x8* h, bf16x8* m, bf16x8* l) {
-    u32x4 H, M, L;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t wh = pack_bf16(v[2 * i], v[2 * i + 1]);
-        const float r0 = v[2 * i] - __builtin_bit_cast(float, wh << 16);
-        const float r1 = v[2 * i + 1] - __builtin_bit_cast(float, wh & 0xFFFF0000u);
-        const uint32_t wm = pack_bf16(r0, r1);
-        const float s0 = r0 - __builtin_bit_cast(float, wm << 16);
-        const float s1 = r1 - __builtin_bit_cast(float, wm & 0xFFFF0000u);
-        H[i] = wh;
-        M[i] = wm;
-        L[i] = pack_bf16(s0, s1);
-    }
-    *h = __builtin_bit_cast(bf16x8, H);
-    *m = __builtin_bit_cast(bf16x8, M);
-    *l = __builtin_bit_cast(bf16x8, L);
-}
 
 // W [cout][cin] (or its transpose [cin][cout] read as the operand of the input gradient) -> fragment stream
 // [step kb][group cg][tile j][plane h | m | l][lane][8 bf16]: lane (mi = lane % 16, g = lane / 16) of tile j holds

@@ -16,20 +16,11 @@
 //   grouped strided / inverse tables), bias / addend / ReLU epilogue exactly as spconv_split_kernel.
 #include <cstdlib>
 
-#include "common.hpp"
+#include "split_bf16.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
+using namespace sbf;
 
 // x [m, c] fp32 -> xs: hi plane [m + 1, c] bf16 | lo plane [m + 1, c] bf16, row m of both = 0.  One thread = 8 channels.
 __global__ __launch_bounds__(256) void presplit_kernel(const float* __restrict__ x, int64_t m, int c, __bf16* __restrict__ xs) {
@@ -40,13 +31,7 @@ __global__ __launch_bounds__(256) void presplit_kernel(const float* __restrict__
     u32x4 hi = {0u, 0u, 0u, 0u}, lo = {0u, 0u, 0u, 0u};
     if (t < m * (c / 8)) {
         const f32x4 p = *reinterpret_cast<const f32x4*>(x + t * 8), q = *reinterpret_cast<const f32x4*>(x + t * 8 + 4);
-        const float v[8] = {p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3]};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t w = pack_bf16(v[2 * i], v[2 * i + 1]);
-            hi[i] = w;
-            lo[i] = pack_bf16(v[2 * i] - __builtin_bit_cast(float, w << 16), v[2 * i + 1] - __builtin_bit_cast(float, w & 0xFFFF0000u));
-        }
+        split8(p, q, &hi, &lo);
     }
     *reinterpret_cast<u32x4*>(xs + t * 8) = hi;
     *reinterpret_cast<u32x4*>(xs + plane + t * 8) = lo;

@@ -28,7 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.hpp"
+#include "split_bf16.hpp"
 
 #ifdef SEG3D_TILE_DBG
 #define TILE_DBG(d) (d)
@@ -38,38 +38,12 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+using namespace sbf;
 
 constexpr int kTile = 128;       // output rows per tile
 constexpr int kUMax = 512;       // rows of the LDS image
 constexpr int kZeroSlot = 4096;  // first 16-B slot of the all-zero image row (row 512)
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-// 8 floats -> (hi, lo) bf16 fragments; hi = RNE(x), lo = RNE(x - hi)   (as spconv_split.hip's split8)
-__device__ __forceinline__ void split8(const f32x4& p, const f32x4& q, u32x4* hi, u32x4* lo) {
-    u32x4 h, l;
-    const float v[8] = {p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t ph = pack_bf16(v[2 * i], v[2 * i + 1]);
-        const float h0 = __builtin_bit_cast(float, ph << 16);
-        const float h1 = __builtin_bit_cast(float, ph & 0xFFFF0000u);
-        h[i] = ph;
-        l[i] = pack_bf16(v[2 * i] - h0, v[2 * i + 1] - h1);
-    }
-    *hi = h;
-    *lo = l;
-}
 
 // first 16-B slot of image row u: a 256-B bank line holds a row pair; the 16 slots of a pair are XOR-swizzled with the
 // pair index so that lanes reading the same quarter of consecutive rows (the common case: neighbours of consecutive

@@ -21,7 +21,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "attn_common.hpp"
+#include "split_bf16.hpp"
 
 // wgrad_dense_lds.hip: the LDS-shared form for cout % 96 == 0, cin % 48 == 0 (1 = it takes the shape)
 int wgrad_dense_lds_plan(int64_t m, int cin, int cout, int* chunks, int64_t* rows);
@@ -30,7 +30,7 @@ int wgrad_dense_lds_launch(const float* x, const float* dy, int64_t m, int cin, 
 
 namespace {
 
-using namespace attn;
+using namespace sbf;
 
 constexpr int kWaves = 4;
 constexpr int kThreads = 64 * kWaves;
@@ -104,24 +104,6 @@ Plan plan(int64_t m, int cin, int cout, bool allow_lds = false) {
     p.rows = rows;
     p.chunks = (int)((m + rows - 1) / rows);
     return p;
-}
-
-// bf16 fragment of channel `comp` (0..3) of a lane's quad from 8 rows of 4 bf16 each (q[i] = row i: {ch0 | ch1 << 16, ch2 | ch3 << 16})
-__device__ __forceinline__ bf16x8 frag_from_bf16_rows(const uint2* q, int comp) {
-    u32x4 h;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t a = (comp & 2) ? q[2 * j].y : q[2 * j].x, b = (comp & 2) ? q[2 * j + 1].y : q[2 * j + 1].x;
-        h[j] = (comp & 1) ? ((a >> 16) | (b & 0xFFFF0000u)) : ((a & 0xFFFFu) | (b << 16));
-    }
-    return __builtin_bit_cast(bf16x8, h);
-}
-
-// acc += a . b for a split-bf16 `a` and a `b` that IS bf16 (a bf16 row is its own high half: no a_hi * b_lo term)
-__device__ __forceinline__ f32x4 mfma2(const bf16x8& a_hi, const bf16x8& a_lo, const bf16x8& b, f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_lo, b, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_hi, b, acc, 0, 0, 0);
-    return acc;
 }
 
 // XB: the x rows are stored as bf16 (the opt-in bf16 copies a training forward saves for its backward, SEG3D_TRAIN_STORAGE=bf16):

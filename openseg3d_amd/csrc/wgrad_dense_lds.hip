@@ -20,7 +20,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "attn_common.hpp"
+#include "split_bf16.hpp"
 
 int wgrad_dense_lds_plan(int64_t m, int cin, int cout, int* chunks, int64_t* rows);
 int wgrad_dense_lds_launch(const float* x, const float* dy, int64_t m, int cin, int cout, int chunks, int64_t rows, float* part,
@@ -28,12 +28,7 @@ int wgrad_dense_lds_launch(const float* x, const float* dy, int64_t m, int cin, 
 
 namespace {
 
-using namespace attn;
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+using namespace sbf;
 
 // row stride in bytes of a plane with `c` bf16 columns: an odd multiple of 32 bytes, so that the 16 rows a transposed read
 // touches (32 contiguous bytes each) fall into 16 different bank groups
@@ -103,11 +98,8 @@ __global__ __launch_bounds__(64 * WA * WB, 2) void wgrad_dense_lds_kernel(const 
             char* dst = is_y ? y_hi + row * RSY + q * 8 : x_hi + row * RSX + (q - DYC / 4) * 8;
             const int plane = is_y ? PY : PX;
             uint32_t h0, l0, h1, l1;
-            const uint32_t w0 = pack_bf16(raw[i][0], raw[i][1]), w1 = pack_bf16(raw[i][2], raw[i][3]);
-            h0 = w0;
-            h1 = w1;
-            l0 = pack_bf16(raw[i][0] - __builtin_bit_cast(float, w0 << 16), raw[i][1] - __builtin_bit_cast(float, w0 & 0xFFFF0000u));
-            l1 = pack_bf16(raw[i][2] - __builtin_bit_cast(float, w1 << 16), raw[i][3] - __builtin_bit_cast(float, w1 & 0xFFFF0000u));
+            split2(raw[i][0], raw[i][1], &h0, &l0);
+            split2(raw[i][2], raw[i][3], &h1, &l1);
             *reinterpret_cast<u32x2*>(dst) = (u32x2){h0, h1};
             *reinterpret_cast<u32x2*>(dst + plane) = (u32x2){l0, l1};
         }

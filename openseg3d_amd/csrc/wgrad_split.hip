@@ -20,7 +20,7 @@
 // the workgroups that read the same gathered rows are dispatched back to back on one XCD and share its L2.
 #include <cstdlib>
 
-#include "attn_common.hpp"
+#include "split_bf16.hpp"
 
 int wgrad_chunk_reduce(const float* part, int chunks, int64_t n, int64_t nw, float* dw, float* db, hipStream_t st);
 
@@ -47,30 +47,14 @@ extern "C" int seg3d_debug_wgrad_stamps(void* buf) {
 
 namespace {
 
-using namespace attn;
+using namespace sbf;
 
 constexpr int kWaves = 4;
 constexpr int kThreads = 64 * kWaves;
 constexpr int kRing = 128;  // pairs per wave ring: at most 31 left over + 64 new
 
 // XB variants (x rows stored as bf16: the opt-in copies a training forward saves for its backward, SEG3D_TRAIN_STORAGE=bf16):
-// a bf16 row is its own high half -- 8-byte gathers, no split of x, two MFMAs per product.  dy is always fp32.
-// bf16 fragment of channel `comp` (0..3) of a lane's quad from 8 rows of 4 bf16 each (q[i] = {ch0 | ch1 << 16, ch2 | ch3 << 16})
-__device__ __forceinline__ bf16x8 frag_from_bf16_rows(const uint2* q, int comp) {
-    u32x4 h;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint32_t a = (comp & 2) ? q[2 * j].y : q[2 * j].x, b = (comp & 2) ? q[2 * j + 1].y : q[2 * j + 1].x;
-        h[j] = (comp & 1) ? ((a >> 16) | (b & 0xFFFF0000u)) : ((a & 0xFFFFu) | (b << 16));
-    }
-    return __builtin_bit_cast(bf16x8, h);
-}
-
-__device__ __forceinline__ f32x4 mfma2(const bf16x8& a_hi, const bf16x8& a_lo, const bf16x8& b, f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_lo, b, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_hi, b, acc, 0, 0, 0);
-    return acc;
-}
+// a bf16 row is its own high half -- 8-byte gathers, no split of x, two MFMAs per product (frag_from_bf16_rows, mfma2).  dy is always fp32.
 
 struct Plan {
     int nbo, nbi;

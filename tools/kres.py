@@ -5,8 +5,10 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
-         "-Wall", "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage"]
+sys.path.insert(0, ROOT)
+from __graft_entry__ import HIPCC_FLAGS  # noqa: E402
+
+FLAGS = HIPCC_FLAGS + ["-Rpass-analysis=kernel-resource-usage"]
 KEYS = {"VGPRs:": "vgpr", "AGPRs:": "agpr", "ScratchSize [bytes/lane]:": "scratch", "Occupancy [waves/SIMD]:": "occ",
         "LDS Size [bytes/block]:": "lds"}
 
