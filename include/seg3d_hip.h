@@ -926,6 +926,38 @@ int seg3d_dice_loss_bwd(const float* logits, const int64_t* labels, const float*
                         int64_t ignore_index, float smooth, float exponent, const float* class_weight, float loss_weight,
                         float avg_factor, float* dlogits, void* stream);
 
+/*
+ * The options of the cross-entropy family that need more than a per-row pass: nn.CrossEntropyLoss(weight=, ignore_index=)
+ * and OHEMCrossEntropyLoss(keep_ratio=, keep_thresh=, class_weight=) (seg3d/models/losses/ohem_cross_entropy_loss.py:23-38)
+ * on logits [n <= INT32_MAX, c <= 4096] with int64 labels.  Valid rows: label != ignore_index and in [0, c).  Per valid row
+ *   l = w[label] * (lse - x[label]),  w = 1 when class_weight (float [c]) is NULL.
+ *   SEG3D_CE_SELECT_MEAN_WEIGHTED  sum l / sum w[label]                                   (nn.CrossEntropyLoss(weight=w))
+ *   SEG3D_CE_SELECT_MEAN_ALL       sum l / n_valid                                        (the OHEM module, no selector)
+ *   SEG3D_CE_SELECT_THRESH         plain mean of l over the valid rows with softmax(x)[label] < keep_thresh (> 0)
+ *   SEG3D_CE_SELECT_RATIO          plain mean of the kept largest l, kept = (int64)((double)n_valid * keep_ratio) clamped
+ *                                  to n_valid (Python's int(n_valid * keep_ratio), hence the double; keep_ratio > 0)
+ * RATIO is an exact selection on the device (a radix select over an order-preserving integer key of l, no sort, no host
+ * read-back): descending by l, NaN above +inf, -0 = +0; among rows equal to the kept-th value the lowest row indices
+ * are taken, the order of torch.sort(descending=True, stable=True).  A row's l does not depend on its position.
+ * forward : lse [n] (log-sum-exp on counted rows, +inf on all others), stats [2] = {loss, denominator} (sum of weights,
+ *           count, or kept); a denominator of 0 (n = 0, kept = 0, nothing below the threshold, a zero weight sum) gives
+ *           loss 0 where torch gives NaN.  Invalid arguments are refused before anything is enqueued.
+ * backward: dlogits = w[label] * (softmax - onehot) * grad_out[0] / denominator on counted rows, exactly 0 elsewhere and
+ *           everywhere when the denominator is 0.
+ * Bit-reproducible: integer atomics only (histogram counts), float64 partial sums folded in a fixed order.
+ */
+#define SEG3D_CE_SELECT_MEAN_WEIGHTED 0
+#define SEG3D_CE_SELECT_MEAN_ALL 1
+#define SEG3D_CE_SELECT_THRESH 2
+#define SEG3D_CE_SELECT_RATIO 3
+size_t seg3d_ce_select_workspace_bytes(int64_t n);
+int seg3d_ce_select_fwd(const float* logits, const int64_t* labels, int64_t n, int32_t c, int64_t ignore_index,
+                        const float* class_weight, int32_t mode, float keep_thresh, double keep_ratio, float* lse,
+                        float* stats, void* workspace, size_t workspace_bytes, void* stream);
+int seg3d_ce_select_bwd(const float* logits, const int64_t* labels, const float* class_weight, const float* lse,
+                        const float* stats, const float* grad_out, int64_t n, int32_t c, int32_t mode, float* dlogits,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Evaluation path (csrc/eval.hip): tools/eval.py:35-64 with --tta, test_time_aug.py:15-35 (MultiScaleFlipAug),
  * seg3d/core/evaluation/iou_metric.py:21-53 (IOUMetric.fast_hist / add).  None of the three allocates.

@@ -10,11 +10,14 @@
 Same class names, constructor arguments and ``loss_name`` properties.  The configurations build_criterion can produce
 (OHEM by probability threshold, multi-class Lovasz over the whole batch) run in libseg3d_hip.so: one pass each way for
 the cross-entropy terms, one device sort for all classes of the Lovasz term -- and compute_loss, given such a list, makes one
-call for all heads and both terms (ops.fused_criterion, same bits).  Options the builder never sets (OHEM by
-keep_ratio, per-image / binary Lovasz) are composed from torch ops on the same device tensors.  FocalLoss and DiceLoss,
-which no configuration of the reference builds but its package exports, run in the library too on CUDA float32 inputs
-(build_criterion keys 'focal' and 'dice', beyond the reference's three); other inputs take a torch composition of the
-same formulas.
+call for all heads and both terms (ops.fused_criterion, same bits).  The cross-entropy options the reference's builder
+never sets -- class weights (nn.CrossEntropyLoss(weight=), OHEMCrossEntropyLoss(class_weight=)) and OHEM by keep_ratio, an
+exact device-side selection of the hardest rows without a read-back -- run in the library as well on CUDA float32 inputs
+(seg3d_ce_select_fwd / _bwd; build_criterion keys 'weighted_ce' and 'ohem_ce_ratio', which consume DATASET.CLASS_WEIGHT
+and MODEL.OHEM_KEEP_RATIO), as terms of compute_loss's per-term loop.  Per-image / binary Lovasz are composed from torch
+ops on the same device tensors.  FocalLoss and DiceLoss, which no configuration of the reference builds but its package
+exports, run in the library too on CUDA float32 inputs (build_criterion keys 'focal' and 'dice', beyond the reference's
+three); other inputs take a torch composition of the same formulas.
 """
 import contextlib
 import os
@@ -27,40 +30,79 @@ import torch.nn.functional as F
 from . import ops
 
 
-class CrossEntropyLoss(nn.Module):
-    """nn.CrossEntropyLoss(ignore_index=...) (builder.py:29-30) through seg3d_cross_entropy_fwd/bwd."""
+class _ClassWeightCache:
+    """The class weights as a float32 tensor on the logits' device, uploaded once per device instead of per call."""
 
-    def __init__(self, ignore_index=255, loss_name="loss_cross_entropy"):
+    def _device_weight(self, device):
+        if self.class_weight is None:
+            return None
+        cache = self.__dict__.setdefault("_weight_cache", {})
+        if device not in cache:
+            w = self.class_weight
+            cache[device] = torch.as_tensor(w if torch.is_tensor(w) else np.asarray(w), dtype=torch.float32).to(device)
+        return cache[device]
+
+    def _weight_like(self, inputs):
+        """For the torch compositions: the weights in the logits' dtype, on their device."""
+        w = self.class_weight
+        if w is None:
+            return None
+        return w.to(inputs) if torch.is_tensor(w) else inputs.new_tensor(np.asarray(w))
+
+
+class CrossEntropyLoss(nn.Module, _ClassWeightCache):
+    """nn.CrossEntropyLoss(ignore_index=...) (builder.py:29-30) through seg3d_cross_entropy_fwd/bwd.  ``class_weight`` (a
+    list, or the path of an .npy file): nn.CrossEntropyLoss(weight=..., ignore_index=...), the mean weighted by the
+    targets' class weights, through seg3d_ce_select_fwd/bwd on CUDA float32 inputs and F.cross_entropy elsewhere."""
+
+    def __init__(self, ignore_index=255, class_weight=None, loss_name="loss_cross_entropy"):
         super().__init__()
         self.ignore_index = ignore_index
+        self.class_weight = get_class_weight(class_weight)
         self._loss_name = loss_name
 
     def forward(self, inputs, targets):
-        return ops.cross_entropy(inputs, targets, ignore_index=self.ignore_index)
+        if self.class_weight is None:
+            return ops.cross_entropy(inputs, targets, ignore_index=self.ignore_index)
+        if ops._loss_args_ok(inputs, targets, 4096):
+            return ops.cross_entropy_select(inputs, targets, ignore_index=self.ignore_index,
+                                            class_weight=self._device_weight(inputs.device), weighted_mean=True)
+        return F.cross_entropy(inputs, targets, weight=self._weight_like(inputs), ignore_index=self.ignore_index)
 
     @property
     def loss_name(self):
         return self._loss_name
 
 
-class OHEMCrossEntropyLoss(nn.Module):
+class OHEMCrossEntropyLoss(nn.Module, _ClassWeightCache):
+    """ohem_cross_entropy_loss.py:5-38.  keep_ratio wins over keep_thresh (the reference's if / elif).  Without class
+    weights and without keep_ratio: seg3d_cross_entropy_fwd/bwd.  With either, CUDA float32 inputs run in
+    seg3d_ce_select_fwd/bwd (keep_ratio: an exact device-side selection of the int(n_valid * keep_ratio) largest losses,
+    no read-back); other inputs (CPU, float64) take the torch composition of the reference's lines.  Equal losses at the
+    keep_ratio cut are taken in row order on both paths (a stable sort; the reference's own sort leaves it open, the
+    value does not depend on it).  The mean over nothing is 0 on the kernel paths (NaN in torch)."""
+
     def __init__(self, keep_ratio=None, keep_thresh=None, ignore_index=255, class_weight=None,
                  loss_name="loss_ohem_cross_entropy"):
         super().__init__()
         self.keep_ratio, self.keep_thresh = keep_ratio, keep_thresh
-        self.ignore_index, self.class_weight = ignore_index, class_weight
+        self.ignore_index, self.class_weight = ignore_index, get_class_weight(class_weight)
         self._loss_name = loss_name
 
     def forward(self, inputs, targets):
         if self.class_weight is None and not self.keep_ratio:
             # keep_thresh (what build_criterion passes) or plain CE: fused kernel, no [n, C] softmax materialised
             return ops.cross_entropy(inputs, targets, ignore_index=self.ignore_index, keep_thresh=self.keep_thresh)
+        if ops._loss_args_ok(inputs, targets, 4096):
+            return ops.cross_entropy_select(inputs, targets, ignore_index=self.ignore_index,
+                                            class_weight=self._device_weight(inputs.device), keep_ratio=self.keep_ratio,
+                                            keep_thresh=self.keep_thresh)
         mask = targets != self.ignore_index
-        losses = F.cross_entropy(inputs, targets, weight=self.class_weight, ignore_index=self.ignore_index,
+        losses = F.cross_entropy(inputs, targets, weight=self._weight_like(inputs), ignore_index=self.ignore_index,
                                  reduction="none")[mask]
         if self.keep_ratio:  # ohem_cross_entropy_loss.py:27-30: the hardest keep_ratio of the valid rows
             kept = int(losses.shape[0] * self.keep_ratio)
-            losses = torch.topk(losses, kept, sorted=False)[0]
+            losses = losses[torch.sort(losses, descending=True, stable=True)[1][:kept]]
         elif self.keep_thresh:
             probs = F.softmax(inputs, dim=1)[mask].gather(1, targets[mask].unsqueeze(1)).squeeze(1)
             losses = losses[probs < self.keep_thresh]
@@ -132,18 +174,6 @@ def get_class_weight(class_weight):
 def _on_device_path(inputs, targets):
     return (inputs.is_cuda and inputs.dtype == torch.float32 and inputs.dim() == 2 and inputs.shape[1] <= 64
             and targets.dtype == torch.int64 and targets.dim() == 1)
-
-
-class _ClassWeightCache:
-    """The class weights as a float32 tensor on the logits' device, uploaded once per device instead of per call."""
-
-    def _device_weight(self, device):
-        if self.class_weight is None:
-            return None
-        cache = self.__dict__.setdefault("_weight_cache", {})
-        if device not in cache:
-            cache[device] = torch.as_tensor(np.asarray(self.class_weight), dtype=torch.float32).to(device)
-        return cache[device]
 
 
 class FocalLoss(nn.Module, _ClassWeightCache):
@@ -246,13 +276,20 @@ class DiceLoss(nn.Module, _ClassWeightCache):
 
 def build_criterion(cfg, dataset):
     """seg3d/models/builder.py:26-40: list of (criterion, weight) in MODEL.LOSSES order.  'focal' and 'dice' go beyond the
-    reference's three keys: its package exports the two classes, its builder has no key for them."""
+    reference's three keys: its package exports the two classes, its builder has no key for them.  So do 'weighted_ce'
+    (CrossEntropyLoss with DATASET.CLASS_WEIGHT) and 'ohem_ce_ratio' (OHEM by MODEL.OHEM_KEEP_RATIO): two configuration
+    keys the reference ships and nothing of it reads."""
     losses = []
     for name in cfg.MODEL.LOSSES:
         if name == "ce":
             criterion = CrossEntropyLoss(ignore_index=dataset.ignore_index)
         elif name == "ohem_ce":
             criterion = OHEMCrossEntropyLoss(keep_thresh=cfg.MODEL.OHEM_KEEP_THRESH, ignore_index=dataset.ignore_index)
+        elif name == "weighted_ce":  # DATASET.CLASS_WEIGHT finds a consumer; an empty list means no weights
+            criterion = CrossEntropyLoss(ignore_index=dataset.ignore_index,
+                                         class_weight=list(cfg.DATASET.CLASS_WEIGHT) or None)
+        elif name == "ohem_ce_ratio":
+            criterion = OHEMCrossEntropyLoss(keep_ratio=cfg.MODEL.OHEM_KEEP_RATIO, ignore_index=dataset.ignore_index)
         elif name == "lovasz":
             criterion = LovaszLoss(ignore_index=dataset.ignore_index)
         elif name == "focal":
@@ -276,7 +313,7 @@ def _fused_terms(criterion):
     the two alone; None for any other list (focal, dice, class weights, OHEM by ratio, another order)."""
     ce = lov = None
     for fn, w in criterion:
-        if lov is None and ce is None and type(fn) is CrossEntropyLoss:
+        if lov is None and ce is None and type(fn) is CrossEntropyLoss and fn.class_weight is None:
             ce = (fn.ignore_index, None, w)
         elif (lov is None and ce is None and type(fn) is OHEMCrossEntropyLoss and fn.class_weight is None
               and not fn.keep_ratio):

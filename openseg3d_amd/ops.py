@@ -2339,6 +2339,62 @@ def _class_weight_f32(class_weight, c, device, what):
     return w
 
 
+CE_MEAN_WEIGHTED, CE_MEAN_ALL, CE_THRESH, CE_RATIO = 0, 1, 2, 3  # SEG3D_CE_SELECT_* of include/seg3d_hip.h
+
+
+class _CrossEntropySelectFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, class_weight, mode, keep_thresh, keep_ratio):
+        x = _f32c(logits)
+        n, c = x.shape
+        lab = labels.contiguous()
+        lse = torch.empty((n,), dtype=torch.float32, device=x.device)
+        stats = torch.empty((2,), dtype=torch.float32, device=x.device)
+        ws_bytes = _lib.query("seg3d_ce_select_workspace_bytes", n)
+        ws = _workspace(ws_bytes, x.device)
+        _lib.call("seg3d_ce_select_fwd", _ptr(x), _ptr(lab), n, c, int(ignore_index),
+                  _ptr(class_weight) if class_weight is not None else None, mode, float(keep_thresh), float(keep_ratio),
+                  _ptr(lse), _ptr(stats), _ptr(ws), ws_bytes, _stream())
+        ctx.save_for_backward(x, lab, lse, stats, class_weight)
+        ctx.mode = mode
+        return stats[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, lab, lse, stats, class_weight = ctx.saved_tensors
+        n, c = x.shape
+        dx = torch.empty_like(x)
+        gg = _f32c(g.reshape(1))
+        _lib.call("seg3d_ce_select_bwd", _ptr(x), _ptr(lab), _ptr(class_weight) if class_weight is not None else None,
+                  _ptr(lse), _ptr(stats), _ptr(gg), n, c, ctx.mode, _ptr(dx), _stream())
+        return dx, None, None, None, None, None, None
+
+
+def cross_entropy_select(logits, labels, ignore_index=-100, class_weight=None, keep_ratio=None, keep_thresh=None,
+                         weighted_mean=False):
+    """The cross-entropy options that need more than a per-row pass, for float32 [n, C <= 4096] logits and int64 labels on
+    the GPU, one library call each way (seg3d_ce_select_fwd / _bwd).  Per valid row l = class_weight[label] * CE(row).
+      ``weighted_mean``  sum l / sum class_weight[label]: ``F.cross_entropy(weight=class_weight, ignore_index=...)``;
+      otherwise the reference's OHEMCrossEntropyLoss (ohem_cross_entropy_loss.py:23-38), a plain mean of l over
+      ``keep_ratio``   the int(n_valid * keep_ratio) largest l -- selected on the device, no read-back; equal losses are
+                       taken in row order, as torch.sort(descending=True, stable=True) ranks them; it wins over
+      ``keep_thresh``  the valid rows whose (unweighted) softmax probability of the target is below it; or, with neither,
+      all valid rows.
+    Returns 0 (not NaN) when nothing is counted or the weights of the counted rows sum to 0."""
+    if not _loss_args_ok(logits, labels, 4096):
+        raise ValueError("cross_entropy_select: float32 [n, C <= 4096] logits and int64 [n] labels on the GPU")
+    if weighted_mean and (keep_ratio or keep_thresh):
+        raise ValueError("cross_entropy_select: weighted_mean is nn.CrossEntropyLoss's mean, it takes no selector")
+    if keep_ratio and not float(keep_ratio) > 0.0:
+        raise ValueError("cross_entropy_select: keep_ratio > 0")
+    if not keep_ratio and keep_thresh and not float(keep_thresh) > 0.0:
+        raise ValueError("cross_entropy_select: keep_thresh > 0")
+    w = _class_weight_f32(class_weight, logits.shape[1], logits.device, "cross_entropy_select")
+    mode = CE_MEAN_WEIGHTED if weighted_mean else CE_RATIO if keep_ratio else CE_THRESH if keep_thresh else CE_MEAN_ALL
+    return _CrossEntropySelectFn.apply(logits, labels, ignore_index, w, mode, keep_thresh if mode == CE_THRESH else 0.0,
+                                       keep_ratio if mode == CE_RATIO else 0.0)
+
+
 class _FocalLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, ignore_index, gamma, alpha, class_weight, reduction):
