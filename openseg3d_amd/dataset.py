@@ -18,10 +18,16 @@ device: ``seg3d_frame_assemble`` (one launch per frame for all sweeps), the labe
 ``filename`` and (testing) ``points_ri``.  Voxelization runs in the dtype the reference voxelizes in (the file's own
 dtype without augmentation, float32 after it), per frame, so the voxel ids are the reference's; the float32 cast for the
 model comes after.
+
+``sweep_cache=n`` (validation / testing on the device) keeps the last ``n`` uploaded sweeps in HBM.  ``load_raw`` then
+reads the current sweep only and names the history sweeps (``sweeps[s] is None``, ``sweep_names``); ``assemble`` takes
+them from the cache, reads and uploads a missing one itself, and puts the current sweep in afterwards.  Frames taken in
+order then read and upload every lidar file once instead of ``NUM_SWEEPS`` times; the batch is the same bit
+for bit in any order.
 """
 import glob
 import os
-from collections import defaultdict
+from collections import OrderedDict, defaultdict
 
 import numpy as np
 import torch
@@ -33,7 +39,7 @@ from .batch import VoxelGenerator
 
 
 class WaymoDataset(Dataset):
-    def __init__(self, cfg, data_root, mode='training', device=None, rng="device", instance_bank=None):
+    def __init__(self, cfg, data_root, mode='training', device=None, rng="device", instance_bank=None, sweep_cache=None):
         assert mode in ['training', 'validation', 'testing']
         self.cfg = cfg
         self.data_root = data_root
@@ -41,6 +47,18 @@ class WaymoDataset(Dataset):
         self.device = None if device is None else torch.device(device)
         if self.device is not None and self.device.type != "cuda":
             raise Seg3dError("device is None (the host entries) or a CUDA device")
+        # sweep_cache = n: the last n uploaded sweeps stay on the device, keyed by file name, and ``assemble`` takes a
+        # frame's history sweeps from there (frames evaluated in order share all but one sweep with their predecessor)
+        if sweep_cache is not None:
+            if self.device is None:
+                raise ValueError("sweep_cache keeps uploaded sweeps on the device: it needs device='cuda'")
+            if mode == 'training':
+                raise ValueError("sweep_cache is for frames read in order: training draws its history sweeps at random "
+                                 "and shuffles frames")
+            if int(sweep_cache) < 1:
+                raise ValueError(f"sweep_cache={sweep_cache}: the number of sweeps kept, at least 1")
+        self.sweep_cache = None if sweep_cache is None else int(sweep_cache)
+        self._resident_sweeps = OrderedDict()  # file name -> uploaded [N, DIM_POINT] rows, least recently used first
 
         all_filenames = self.get_dir_filenames('lidar')
         self.file_idx_to_name = self.build_file_idx_to_name(all_filenames)
@@ -353,8 +371,13 @@ class WaymoDataset(Dataset):
                                                     self.cfg.DATASET.MAX_NUM_SWEEPS)
         else:
             names, matrices, lags = [filename], [None], [0.0]
-        raws = [self._raw_points(n) for n in names]
-        raw = {'filename': filename, 'sweeps': [r[:, :dim] for r in raws], 'matrices': matrices, 'lags': lags}
+        if self.sweep_cache is None:
+            raws = [self._raw_points(n) for n in names]
+            raw = {'filename': filename, 'sweeps': [r[:, :dim] for r in raws], 'matrices': matrices, 'lags': lags}
+        else:  # the history sweeps by name only: ``assemble`` has them on the device, or reads them on a miss
+            raws = [self._raw_points(filename)]
+            raw = {'filename': filename, 'sweeps': [raws[0][:, :dim]] + [None] * (len(names) - 1), 'matrices': matrices,
+                   'lags': lags, 'sweep_names': names}
         if self.use_image_feature:
             raw['image_rows'], raw['image_feats'] = self._raw_image_features(filename)
         if self.mode != 'testing':
@@ -379,6 +402,31 @@ class WaymoDataset(Dataset):
     def _upload(self, a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
 
+    def _resident_sweep(self, name, rows=None):
+        """The uploaded [N, DIM_POINT] rows of lidar file ``name`` through the LRU of ``sweep_cache`` sweeps.  rows: the
+        file's rows when the caller has just read them (the current sweep), which are uploaded and replace the entry;
+        otherwise a miss reads the file here, in the calling process."""
+        cache = self._resident_sweeps
+        if rows is None and name in cache:
+            cache.move_to_end(name)
+            return cache[name]
+        t = self._upload(self._raw_points(name)[:, :self.dim_point] if rows is None else rows)
+        cache[name] = t
+        cache.move_to_end(name)
+        while len(cache) > self.sweep_cache:
+            cache.popitem(last=False)
+        return t
+
+    def _uploaded_sweeps(self, raw):
+        """Every sweep of a ``load_raw`` result on the device, current first."""
+        if self.sweep_cache is None:
+            return [self._upload(s) for s in raw['sweeps']]
+        names = raw.get('sweep_names', [raw['filename']])
+        # history first: the current sweep enters the cache after the frame has taken what it needs from it
+        history = [self._resident_sweep(n) if s is None else self._upload(s)
+                   for n, s in zip(names[1:], raw['sweeps'][1:])]
+        return [self._resident_sweep(names[0], raw['sweeps'][0])] + history
+
     def _labels_on_device(self, raw_labels):
         lab = self._upload(raw_labels).long() - 1
         lab[lab == -1] = 255
@@ -401,8 +449,7 @@ class WaymoDataset(Dataset):
         pts, coords, ids, labels, vlabels, feats, ri = [], [], [], [], [], [], []
         row_offsets, voxel_id_offset, n_vox, n_cur_total = [], [], 0, 0
         for b, raw in enumerate(raw_list):
-            table = ops.sweep_table([self._upload(s) for s in raw['sweeps']], raw['matrices'], raw['lags'],
-                                    dim=self.dim_point)
+            table = ops.sweep_table(self._uploaded_sweeps(raw), raw['matrices'], raw['lags'], dim=self.dim_point)
             n_cur = int(raw['sweeps'][0].shape[0])
             plain = not self._augments and not self.use_cylinder
             out = ops.frame_assemble(table, want=("rows", "collated") if plain else ("rows",), batch_id=b)

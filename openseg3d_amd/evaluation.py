@@ -10,6 +10,11 @@ one launch (seg3d_tta_views_f32), voxelizes K views at a time on the device as o
 forward's softmax into a running sum (seg3d_softmax_accumulate_f32); ``segment_frame`` takes the argmax and feeds the
 confusion matrix in the same pass (seg3d_argmax_confusion).  The list form ``MultiScaleFlipAug.__call__`` stays for
 the reference's loop as written.
+
+Multi-sweep frames (configs/waymo_multi_sweeps.yaml), which the reference's views cannot carry (test_time_aug.py:23-24
+copies no ``cur_point_indices``): a view transforms x, y, z of every row, current and history; the current rows are those
+whose lag column is exactly 0, and the result has one row per current row, in the order of ``point_labels``,
+``points_ri`` and ``point_image_features``.  Each view searches its own fusion kNN.
 """
 import warnings
 
@@ -126,6 +131,16 @@ def _cartesian_rows(points, dataset):
     return points
 
 
+def _current_row_count(data_dict):
+    """point_id_offset[-1] of a one-frame batch: the python ints of the device batch builders where they are there
+    (no read-back), else the collated array or tensor."""
+    offsets = data_dict.get("point_row_offsets")
+    if offsets is None:
+        offsets = data_dict["point_id_offset"]
+        offsets = offsets.tolist() if torch.is_tensor(offsets) else np.asarray(offsets).reshape(-1).tolist()
+    return int(offsets[-1])
+
+
 class MultiScaleFlipAug:
     """test_time_aug.py:6-43, same constructor and attributes.  ``__call__`` is the reference's list form (one collated
     dict per view, built by the library's host views routine, then ``dataset.prepare_data`` / ``collate_batch``);
@@ -152,11 +167,16 @@ class MultiScaleFlipAug:
         frame = np.ascontiguousarray(_cartesian_rows(points, self.dataset), dtype=np.float32)
         views = ops.tta_views_host(frame, self.table())
         n = frame.shape[0]
+        # multi-sweep: prepare_data reads cur_point_indices (waymo_dataset.py:266), which the reference's views lack; the
+        # views keep the lag column, so the current rows of every view are the frame's
+        cur = np.flatnonzero(frame[:, 3] == 0) if getattr(self.dataset, "use_multi_sweeps", False) else None
         aug_data_list = []
         for v in range(self.n_views):
             new_data = dict()
             if data.get("point_image_features") is not None:
                 new_data["point_image_features"] = np.array(data["point_image_features"], copy=True)
+            if cur is not None:
+                new_data["cur_point_indices"] = cur.copy()
             new_data["points"] = views[v * n:(v + 1) * n, 1:].copy()
             new_data = self.dataset.prepare_data(new_data)
             new_data = self.dataset.collate_batch([new_data])
@@ -172,13 +192,23 @@ class MultiScaleFlipAug:
             raise ValueError(f"views_per_forward={k} x batch {batch_size} scenes exceeds the kernels' {MAX_BATCH}")
         return k
 
+    @staticmethod
+    def _view_current_rows(points, j, n, cur):
+        """The rows of view ``j`` of a collated K-view batch that the model's point branch reads, without the batch
+        column: all ``n`` of them, or the current ones of a multi-sweep frame."""
+        rows = points[j * n:(j + 1) * n, 1:]
+        return rows if cur is None else rows[cur]
+
     def accumulate(self, model, data_dict, views_per_forward=None):
-        """Sum over the views of the per-view softmax, float32 [N, C] on the device, and the number of views."""
+        """Sum over the views of the per-view softmax, float32 [N, C] on the device, and the number of views.  For a
+        multi-sweep dataset a view transforms every row, current and history, and N is the number of current rows (lag
+        column exactly 0, the model's own rule), in their order in the frame."""
         if model.training:
             raise RuntimeError("MultiScaleFlipAug.predict needs model.eval(): DropPath / dropout would randomize the views")
-        if getattr(self.dataset, "use_multi_sweeps", False):
-            raise NotImplementedError("test-time augmentation of multi-sweep frames (prepare_data needs cur_point_indices, "
-                                      "which the reference's views lack)")
+        multi = bool(getattr(self.dataset, "use_multi_sweeps", False))
+        if multi and data_dict.get("point_id_offset") is None:
+            raise NotImplementedError("test-time augmentation of a multi-sweep frame needs its point_id_offset (the number "
+                                      "of current-sweep rows; collate_batch, assemble and batch_from_resident all set it)")
         bs = int(data_dict.get("batch_size", 1))
         if bs != 1:
             raise ValueError(f"MultiScaleFlipAug.predict takes one frame, got batch_size={bs} (the reference's "
@@ -193,19 +223,40 @@ class MultiScaleFlipAug:
         if img is not None:
             img = (torch.from_numpy(img) if isinstance(img, np.ndarray) else img).to(device=dev, dtype=torch.float32)
         n, n_views = frame.shape[0], self.n_views
+        n_out, cur, cur_rows = n, None, None
+        if multi:
+            # the current rows, found once per frame (nonzero reads their count back); view j of a forward has them at
+            # j * N + cur, which travels with the batch so that the model does not search each forward again
+            cur = torch.nonzero(frame[:, 3] == 0).view(-1)
+            n_out = int(cur.shape[0])
+            want = _current_row_count(data_dict)
+            if n_out != want:
+                raise ValueError(f"{n_out} rows of the frame have time lag 0, point_id_offset says {want} current rows")
+            cur_rows = (torch.arange(k_per, device=dev).view(-1, 1) * n + cur.view(1, -1)).reshape(-1)
         views = ops.tta_views(frame, self.table(batch_period=k_per))  # all views, one launch; column 0 = v % K
         cylinder = bool(getattr(self.dataset, "use_cylinder", False))
         vs = [float(v) for v in self.dataset.voxel_size]
         pcr = [float(v) for v in self.dataset.point_cloud_range]
+        # DeepFusion's neighbour search, planned here view by view.  The search strides the [N, D] rows by 3 floats, as the
+        # reference's kernel does (ops.knn_query), so in a batch of K frames the segment of frame j > 0 lies over other
+        # frames' rows: searched with the batch, a view's neighbours would depend on K.  Each view is searched alone, in its
+        # own coordinates, exactly as its batch-1 forward searches it, and its rows are shifted to its place in the batch.
+        search = getattr(getattr(model, "deep_fusion", None), "neighbours", None) if img is not None else None
+        one = torch.tensor([n_out], dtype=torch.int32, device=dev)
         acc = None
         with torch.no_grad():
             for k0 in range(0, n_views, k_per):
                 k = min(k_per, n_views - k0)
-                b = B.batch_from_resident(views[k0 * n:(k0 + k) * n], [n * (j + 1) for j in range(k)], vs, pcr,
+                b = B.batch_from_resident(views[k0 * n:(k0 + k) * n], [n_out * (j + 1) for j in range(k)], vs, pcr,
                                           None if img is None else img.repeat(k, 1), cylinder)
+                if multi:
+                    b["cur_rows"] = cur_rows[:k * n_out]
+                if search is not None:
+                    b["fusion_knn"] = torch.cat([search(self._view_current_rows(b["points"], j, n, cur), one) + j * n_out
+                                                 for j in range(k)])
                 logits = model(b)["point_out"]
                 if acc is None:
-                    acc = torch.empty((n, logits.shape[1]), dtype=torch.float32, device=dev)
+                    acc = torch.empty((n_out, logits.shape[1]), dtype=torch.float32, device=dev)
                 ops.softmax_accumulate(logits, acc, first=k0 == 0)
         return acc, n_views
 
@@ -249,8 +300,7 @@ def segment_frame(model, data_dict, augmentor=None, metric=None, views_per_forwa
 
 def segment_test_frame(model, batch, augmentor=None, n_classes=None, views_per_forward=None):
     """``semseg_for_one_frame`` of tools/test.py:37-61 without the protobuf: the frame's predicted labels (argmax of the
-    logits, or of ``MultiScaleFlipAug``'s mean probability for single-sweep configs) written into the two range images of
-    the top lidar on the device (seg3d_range_image_labels; submission.py:27-41).  ``batch``: one frame with ``points_ri``
+    logits, or of ``MultiScaleFlipAug``'s mean probability) written into the two range images of the top lidar on the device (seg3d_range_image_labels; submission.py:27-41).  ``batch``: one frame with ``points_ri``
     and ``filename``, as ``WaymoDataset(mode='testing')`` delivers it.  Returns ``context_name``,
     ``frame_timestamp_micros`` and the int32 [64, 2650, 2] numpy images ``ri_return1`` / ``ri_return2``; packing them
     into Waymo's SegmentationFrame proto needs ``waymo_open_dataset`` and is left to the caller."""

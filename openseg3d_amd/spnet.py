@@ -274,7 +274,9 @@ class SPNet(nn.Module):
         if segformer_mod.PLAN_FIRST and "site_level" not in batch_dict:
             self.voxel_encoder.prepare(batch_dict)
         if self.use_multi_sweeps:
-            cur_rows = torch.nonzero(points[:, 3] == 0).view(-1)  # spnet.py:97
+            cur_rows = batch_dict.get("cur_rows")  # found by the batch's builder (MultiScaleFlipAug), else here
+            if cur_rows is None:
+                cur_rows = torch.nonzero(points[:, 3] == 0).view(-1)  # spnet.py:97
             cur_points, cur_ids, cur_seg = points[cur_rows], seg.ids[cur_rows], None
             batch_rows = batch_dict["points"][cur_rows, 0]
         else:
@@ -287,7 +289,7 @@ class SPNet(nn.Module):
         fused = torch.cat([point_features, point_voxel_features], dim=1)
         if self.use_image_feature:
             img = self.deep_fusion(cur_points, batch_dict["point_id_offset"].int(), fused,
-                                   batch_dict["point_image_features"])
+                                   batch_dict["point_image_features"], batch_dict.get("fusion_knn"))
             fused = torch.cat([fused, img], dim=1)
         fused = self.fusion_encoder(fused)
         row_offsets = batch_dict.get("point_row_offsets")

@@ -14,7 +14,10 @@ float64 [N, 15] rows of a lidar file; history sweeps carry a real pose product. 
                         resident time, as a fraction of 8 TB/s
 then the range-image loop (frame_ref.range_images, the reference's per-point Python loop) against
 seg3d_range_image_labels on one sweep's points, and WaymoDataset(device="cuda").assemble end to end for a validation
-batch of 2 multi-sweep frames read from a temporary directory (file reading timed apart).
+batch of 2 multi-sweep frames read from a temporary directory (file reading timed apart).  Last, 8 consecutive frames
+in frame order, one ``load_raw`` + ``assemble`` each, at NUM_SWEEPS = 3 and 5: ``sweep_cache`` off (every history sweep
+read and uploaded again) against on (each file read and uploaded once), ms per frame with the file reads, bytes uploaded
+per frame and files read.
 Times are medians over the iterations after a warm-up; one stream, synchronised around each call.  Prints one JSON line."""
 import argparse
 import json
@@ -105,6 +108,50 @@ def write_dataset(root, raws):
         np.savetxt(os.path.join(root, "pose", name + ".txt"), pose(i))
 
 
+def sweep_cache_numbers(root, n_sweeps, dev, passes):
+    """One pass over the directory's frames in frame order, ``load_raw`` + ``assemble`` of one frame at a time, from a
+    cold cache: per frame the wall time (files included: the cache moves the history reads from ``load_raw`` into
+    ``assemble`` and drops most of them), the bytes uploaded and the lidar files read."""
+    cfg = config.default_cfg()
+    cfg.DATASET.USE_MULTI_SWEEPS = True
+    cfg.DATASET.NUM_SWEEPS = n_sweeps
+
+    def one_pass(cache):
+        ds = WaymoDataset(cfg, root, "validation", device=dev, sweep_cache=cache)
+        order = sorted(range(len(ds)), key=lambda i: ds.parse_filename(ds.filenames[i])[1])
+        count = {"bytes": 0, "files": 0}
+        upload, raw_points = ds._upload, ds._raw_points
+
+        def counting_upload(a):
+            t = upload(a)
+            count["bytes"] += t.numel() * t.element_size()
+            return t
+
+        def counting_read(name):
+            count["files"] += 1
+            return raw_points(name)
+
+        ds._upload, ds._raw_points = counting_upload, counting_read
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in order:
+            ds.assemble([ds[i]])
+        torch.cuda.synchronize()
+        n = len(order)
+        return {"ms_per_frame": (time.perf_counter() - t0) * 1e3 / n, "uploaded_bytes_per_frame": count["bytes"] / n,
+                "lidar_files_read": count["files"], "frames": n}
+
+    out = {}
+    for key, cache in (("cache_off", None), ("cache_on", cfg.DATASET.MAX_NUM_SWEEPS)):
+        one_pass(cache)  # warm-up: the page cache holds the files afterwards, for both
+        runs = [one_pass(cache) for _ in range(passes)]
+        ms = [r["ms_per_frame"] for r in runs]
+        out[key] = dict(runs[0], ms_per_frame=statistics.median(ms), ms_per_frame_min=min(ms), ms_per_frame_max=max(ms),
+                        passes=passes)
+    out["speedup"] = out["cache_off"]["ms_per_frame"] / out["cache_on"]["ms_per_frame"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -112,7 +159,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    raws = [raw_sweep(s) for s in range(5)]
+    raws = [raw_sweep(s) for s in range(8)]
     out = {"tool": "frame_bench", "status": "measured", "device_name": torch.cuda.get_device_name(0), "iters": args.iters,
            "warmup": args.warmup, "input_dtype": "float64", "dim": DIM}
     for n_sweeps in (3, 5):
@@ -139,6 +186,10 @@ def main():
         batch = ds.assemble(raw_list)
         out["assemble_batch2"] = {"rows": int(batch["points"].shape[0]), "voxels": int(batch["voxel_coords"].shape[0]),
                                   "load_raw_ms": load_ms, "assemble_ms": asm_ms}
+
+    with tempfile.TemporaryDirectory() as root:  # 8 consecutive frames: WaymoDataset(sweep_cache=...) off against on
+        write_dataset(root, raws)
+        out["sweep_cache_8_frames"] = {f"sweeps{n}": sweep_cache_numbers(root, n, dev, 10) for n in (3, 5)}
     line = json.dumps(out)
     print(line)
     if args.out:
