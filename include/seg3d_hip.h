@@ -293,6 +293,15 @@ int seg3d_linear_wgrad_partials(const float* x, const float* dy, int64_t m, int3
 int seg3d_linear_wgrad_partials_xbf16(const uint16_t* x_bf16, const float* dy, int64_t m, int32_t cin, int32_t cout,
                                       int32_t with_bias, void* workspace, size_t workspace_bytes, int32_t* chunks,
                                       void* stream);
+/* ... with x = max(x_pre * scale_in[ch] + shift_in[ch], 0) formed on operand load: the training-mode BatchNorm1d + ReLU in
+ * front of the Linear, from its pre-activation x_pre [m, cin] fp32 and its folded affine (seg3d_batchnorm_stats rows 4, 5).
+ * Split-K kernel with the plan seg3d_linear_wgrad_partials takes for fp32 rows: the same chunks and summation order, hence
+ * the same bits as seg3d_affine_act + seg3d_linear_wgrad_partials.  seg3d_linear_wgrad_bnrelu_fits = 1 when that plan is
+ * the split-K kernel's (the LDS-shared and grouped A/B forms are not covered: EINVAL). */
+int seg3d_linear_wgrad_bnrelu_fits(int64_t m, int32_t cin, int32_t cout);
+int seg3d_linear_wgrad_partials_bnrelu(const float* x_pre, const float* scale_in, const float* shift_in, const float* dy,
+                                       int64_t m, int32_t cin, int32_t cout, int32_t with_bias, void* workspace,
+                                       size_t workspace_bytes, int32_t* chunks, void* stream);
 /* A/B switch of the LDS-shared dense weight-gradient kernel (openseg3d_amd/csrc/wgrad_dense_lds.hip; OFF by default, it did
  * not win): 1 = on, 0 = off, -1 = SEG3D_WGRAD_LDS's choice.  Takes cout % 192 == 0, cin % 96 == 0, m >= 4096; the workspace
  * query covers both kernels. */
@@ -319,6 +328,12 @@ int seg3d_linear_pack_weight_x6(const float* weight, int32_t cin, int32_t cout, 
 int seg3d_linear_fwd_x6(const float* x, int64_t m, const void* w_packed, const float* bias /*or NULL*/,
                         const float* scale /*or NULL*/, const float* shift /*or NULL*/, int32_t relu, int32_t cin,
                         int32_t cout, float* y, void* stream);
+/* ... on the output of a training-mode BatchNorm1d + ReLU formed on operand load: y = max(x_pre * scale_in + shift_in, 0)
+ * W^T (+ bias), x_pre [m, cin] the pre-activation, scale_in / shift_in [cin] the folded affine; cin <= 2048.  The
+ * activated tensor is never written; the result is bit-identical to seg3d_affine_act(relu) + seg3d_linear_fwd_x6. */
+int seg3d_linear_fwd_x6_bnrelu(const float* x_pre, const float* scale_in, const float* shift_in, int64_t m,
+                               const void* w_packed, const float* bias /*or NULL*/, int32_t cin, int32_t cout, float* y,
+                               void* stream);
 
 /* Batched split-bf16 packing: one launch for every conv / Linear weight whose pack is stale (in training all of
  * them, twice: W for forward, W^T for the input gradient).  `jobs` is a DEVICE array of n_jobs records sorted by
@@ -505,6 +520,12 @@ int seg3d_affine_act(const float* x, const float* res, const float* scale, const
 int seg3d_batchnorm_bwd(const float* dy, const float* y, const float* x, const float* mean, const float* rstd,
                         const float* gamma, int32_t relu, int64_t m, int32_t c, float* dx, float* dres,
                         float* sums, void* workspace, size_t workspace_bytes, void* stream);
+/* seg3d_batchnorm_bwd for relu = 1 without a residual, from the pre-activation alone: the ReLU mask is formed as
+ * x * scale + shift > 0 (scale / shift as seg3d_batchnorm_stats left them, rounded as seg3d_affine_act rounds), which is
+ * y > 0 bit for bit; two row reads per pass instead of three, and y need not be kept for the backward. */
+int seg3d_batchnorm_bwd_pre(const float* dy, const float* x, const float* scale, const float* shift, const float* mean,
+                            const float* rstd, const float* gamma, int64_t m, int32_t c, float* dx, float* sums,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* torch.nn.SyncBatchNorm (tools/train.py:246-247, --sync_bn): the two halves of seg3d_batchnorm_bwd as separate
  * entries.  _reduce writes the rank-local sums = {sum g, sum g*xhat} (= dbeta, dgamma of this rank, which is what
  * torch's SyncBatchNorm hands DDP); the caller all-reduces a copy over the ranks and passes it to _apply together

@@ -13,7 +13,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 53
+ABI_VERSION = 54
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -68,10 +68,13 @@ SIGNATURES = {
     "seg3d_linear_packed_bytes_x6": (ctypes.c_size_t, [_i32, _i32]),
     "seg3d_linear_pack_weight_x6": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _p]),
     "seg3d_linear_fwd_x6": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p]),
+    "seg3d_linear_fwd_x6_bnrelu": (ctypes.c_int, [_p, _p, _p, _i64, _p, _p, _i32, _i32, _p, _p]),
     "seg3d_pack_weights_batched": (ctypes.c_int, [_p, _i32, _i64, _p]),
     "seg3d_linear_wgrad_workspace_bytes": (ctypes.c_size_t, [_i64, _i32, _i32]),
     "seg3d_linear_wgrad": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _p, _p, _p, ctypes.c_size_t, _p]),
     "seg3d_linear_wgrad_partials": (ctypes.c_int, [_p, _p, _i64, _i32, _i32, _i32, _p, ctypes.c_size_t, _p, _p]),
+    "seg3d_linear_wgrad_bnrelu_fits": (ctypes.c_int, [_i64, _i32, _i32]),
+    "seg3d_linear_wgrad_partials_bnrelu": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _i32, _i32, _p, ctypes.c_size_t, _p, _p]),
     "seg3d_reduce_partials": (ctypes.c_int, [_p, _i32, _i64, _i64, _p, _p, _p]),
     "seg3d_reduce_partials_batched": (ctypes.c_int, [_p, _i32, _i64, _p]),
     "seg3d_linear_packed_bytes": (_sz, [_i32, _i32, _i32]),
@@ -102,6 +105,7 @@ SIGNATURES = {
     "seg3d_affine_act": (ctypes.c_int, [_p, _p, _p, _p, _i32, _i64, _i32, _p, _p]),
     "seg3d_gelu_fwd": (ctypes.c_int, [_p, _i64, _p, _p, _p]),
     "seg3d_batchnorm_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, ctypes.c_size_t, _p]),
+    "seg3d_batchnorm_bwd_pre": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, ctypes.c_size_t, _p]),
     "seg3d_batchnorm_bwd_reduce": (ctypes.c_int, [_p, _p, _p, _p, _p, _i32, _i64, _i32, _p, _p, ctypes.c_size_t, _p]),
     "seg3d_batchnorm_bwd_apply": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p]),
     "seg3d_segment_reduce_fwd": (ctypes.c_int, [_p, _i32, _p, _p, _i64, _i32, _p, _p, _p]),

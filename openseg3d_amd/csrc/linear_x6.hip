@@ -63,14 +63,20 @@ __global__ __launch_bounds__(256) void pack_x6_kernel(const float* __restrict__ 
 
 // RT = 16-row tiles per wave (4: 256-row workgroups, two per CU; 2: 128-row workgroups, four per CU and the rows requested
 // two steps ahead), WPS = resident workgroups per CU the register allocator leaves room for.
-template <int RT, int WPS>
+// BN (training, seg3d_linear_fwd_x6_bnrelu): the rows are the PRE-activation of a BatchNorm1d + ReLU; the eight raw channel
+// values of a step become fmaxf(v * scale_in[ch] + shift_in[ch], 0) before the split -- a multiply, an add and a max, the
+// separate affine pass's arithmetic bit for bit -- so the activated tensor is never written.  scale_in | shift_in of all
+// cin channels sit in dynamic LDS (2 * cin floats), read per step by the lane that owns the channels.
+template <int RT, int WPS, bool BN = false>
 __global__ __launch_bounds__(kThreads, WPS) void linear_x6_kernel(const float* __restrict__ x, int64_t m_rows,
                                                                   const uint4* __restrict__ wp, const float* __restrict__ bias,
                                                                   const float* __restrict__ scale, const float* __restrict__ shift,
                                                                   int relu, int cin, int cout, float* __restrict__ y, int ncg,
-                                                                  int64_t nrb) {
+                                                                  int64_t nrb, const float* __restrict__ scale_in,
+                                                                  const float* __restrict__ shift_in) {
     constexpr int DEPTH = 2;  // row sets (and W slabs) in flight
     __shared__ __attribute__((aligned(16))) uint4 wl[2][kSlab];
+    extern __shared__ __attribute__((aligned(16))) float affine_in[];  // BN: [scale_in | shift_in][cin]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, c16 = lane & 15;
     // block -> (row block, column group): blocks are dealt round-robin over the 8 XCDs, so id % 8 labels an L2; the column
@@ -89,6 +95,12 @@ __global__ __launch_bounds__(kThreads, WPS) void linear_x6_kernel(const float* _
         xp[i] = x + r * cin + 4 * g;
     }
     const int nkb = cin >> 5;
+    if constexpr (BN) {  // (visible to all waves after the barrier in front of the first step)
+        for (int i = tid; i < cin; i += kThreads) {
+            affine_in[i] = scale_in[i];
+            affine_in[cin + i] = shift_in[i];
+        }
+    }
     const uint4* wsrc = wp + (int64_t)cg * kSlab + tid;  // + kb * ncg * kSlab
     f32x4 raw[DEPTH][RT][2];
     // (slots are compile-time tags: a run-time index would send the register arrays to scratch memory)
@@ -132,10 +144,22 @@ __global__ __launch_bounds__(kThreads, WPS) void linear_x6_kernel(const float* _
         const int cur = kb & 1;
         const bool more = kb + 1 < nkb;  // (uniform)
         bf16x8 xh[RT], xm[RT], xl[RT];
+        f32x4 si[2], ti[2];  // BN: scale_in / shift_in of the lane's channels kb * 32 + 4 g .. + 3 and + 16
+        if constexpr (BN) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                si[h] = *reinterpret_cast<const f32x4*>(affine_in + kb * 32 + 16 * h + 4 * g);
+                ti[h] = *reinterpret_cast<const f32x4*>(affine_in + cin + kb * 32 + 16 * h + 4 * g);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < RT; ++i) {
-            const float v[8] = {raw[SLOT][i][0][0], raw[SLOT][i][0][1], raw[SLOT][i][0][2], raw[SLOT][i][0][3],
-                                raw[SLOT][i][1][0], raw[SLOT][i][1][1], raw[SLOT][i][1][2], raw[SLOT][i][1][3]};
+            float v[8] = {raw[SLOT][i][0][0], raw[SLOT][i][0][1], raw[SLOT][i][0][2], raw[SLOT][i][0][3],
+                          raw[SLOT][i][1][0], raw[SLOT][i][1][1], raw[SLOT][i][1][2], raw[SLOT][i][1][3]};
+            if constexpr (BN) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e] * si[e >> 2][e & 3] + ti[e >> 2][e & 3], 0.f);
+            }
             split3(v, &xh[i], &xm[i], &xl[i]);
         }
         // the rows and the W slab two steps ahead are requested in front of this step's MFMAs (nothing in the last two steps:
@@ -260,13 +284,36 @@ int seg3d_linear_fwd_x6(const float* x, int64_t m, const void* w_packed, const f
     if (blocks > 0x7FFFFFFFll) return SEG3D_EINVAL;
     if (g_x6_rt == 4)
         hipLaunchKernelGGL((linear_x6_kernel<4, 2>), dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), x, m,
-                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb);
+                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb, nullptr,
+                           nullptr);
     else if (g_x6_wps == 4)
         hipLaunchKernelGGL((linear_x6_kernel<2, 4>), dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), x, m,
-                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb);
+                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb, nullptr,
+                           nullptr);
     else
         hipLaunchKernelGGL((linear_x6_kernel<2, 3>), dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), x, m,
-                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb);
+                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb, nullptr,
+                           nullptr);
+    SEG3D_CHECK_LAUNCH();
+    return SEG3D_OK;
+}
+
+/* y[m, cout] = max(x_pre * scale_in + shift_in, 0) W^T (+ bias): seg3d_linear_fwd_x6 on the output of a training-mode
+ * BatchNorm1d + ReLU that is formed on operand load from its pre-activation x_pre [m, cin] and the folded affine
+ * scale_in / shift_in [cin] -- bit-identical to seg3d_affine_act(relu) followed by seg3d_linear_fwd_x6. */
+int seg3d_linear_fwd_x6_bnrelu(const float* x_pre, const float* scale_in, const float* shift_in, int64_t m,
+                               const void* w_packed, const float* bias, int32_t cin, int32_t cout, float* y, void* stream) {
+    // (cin <= 2048: 16 KB of LDS for the affine beside the 24 KB of W slabs keeps three workgroups per CU)
+    if (m < 0 || seg3d_linear_packed_bytes_x6(cin, cout) == 0 || cin > 2048) return SEG3D_EINVAL;
+    if (m == 0) return SEG3D_OK;
+    if (!x_pre || !scale_in || !shift_in || !w_packed || !y) return SEG3D_EINVAL;
+    const int ncg = cout >> 6;
+    const int64_t nrb = (m + 127) / 128;
+    const int64_t blocks = (nrb + 7) / 8 * 8 * ncg;
+    if (blocks > 0x7FFFFFFFll) return SEG3D_EINVAL;
+    hipLaunchKernelGGL((linear_x6_kernel<2, 3, true>), dim3((unsigned)blocks), dim3(kThreads), (size_t)cin * 2 * sizeof(float),
+                       as_stream(stream), x_pre, m, static_cast<const uint4*>(w_packed), bias, nullptr, nullptr, 0, cin, cout, y,
+                       ncg, nrb, scale_in, shift_in);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }

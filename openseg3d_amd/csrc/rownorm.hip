@@ -365,6 +365,82 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_apply_kernel(const float* __r
     }
 }
 
+// BatchNorm + ReLU backward from the pre-activation alone (no residual): y = max(x * scale + shift, 0) is never read,
+// its sign is formed again -- x * scale + shift written as affine_act_kernel writes it (a multiply and an add under
+// -ffp-contract=off), and fmaxf(v, 0) > 0 <=> v > 0 for every v, NaN and -0 included -- so the mask is the same bit
+// for bit and each pass reads two row tensors instead of three.
+__device__ __forceinline__ float4 relu_mask_pre(float4 g, const float4 xv, const float4 s, const float4 b) {
+    const float4 v = make_float4(xv.x * s.x + b.x, xv.y * s.y + b.y, xv.z * s.z + b.z, xv.w * s.w + b.w);
+    g.x = v.x > 0.f ? g.x : 0.f; g.y = v.y > 0.f ? g.y : 0.f;
+    g.z = v.z > 0.f ? g.z : 0.f; g.w = v.w > 0.f ? g.w : 0.f;
+    return g;
+}
+
+// col_reduce_kernel<1> with relu, the mask from (scale, shift): same thread -> (quad, row lane) map, same sums
+__global__ __launch_bounds__(kThreads) void col_reduce_pre_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                  const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift,
+                                                                  const float* __restrict__ mean,
+                                                                  const float* __restrict__ rstd, int64_t m, int c,
+                                                                  float* __restrict__ part /*[gridDim.x][2][c]*/) {
+    extern __shared__ float red[];  // [row lanes][2][c] (<= 8 KiB)
+    const int quads = c / 4;
+    const int lanes = kThreads / quads;
+    const int q = threadIdx.x % quads, rl = threadIdx.x / quads;
+    if (rl < lanes) {
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
+        const float4 p0 = *reinterpret_cast<const float4*>(mean + 4 * q);
+        const float4 p1 = *reinterpret_cast<const float4*>(rstd + 4 * q);
+        const float4 sc = *reinterpret_cast<const float4*>(scale + 4 * q);
+        const float4 sh = *reinterpret_cast<const float4*>(shift + 4 * q);
+        for (int64_t row = (int64_t)blockIdx.x * lanes + rl; row < m; row += (int64_t)gridDim.x * lanes) {
+            const float4 xv = *reinterpret_cast<const float4*>(x + row * c + 4 * q);
+            const float4 g = relu_mask_pre(*reinterpret_cast<const float4*>(dy + row * c + 4 * q), xv, sc, sh);
+            a.x += g.x; a.y += g.y; a.z += g.z; a.w += g.w;
+            b.x += g.x * (xv.x - p0.x) * p1.x; b.y += g.y * (xv.y - p0.y) * p1.y;
+            b.z += g.z * (xv.z - p0.z) * p1.z; b.w += g.w * (xv.w - p0.w) * p1.w;
+        }
+        *reinterpret_cast<float4*>(red + (size_t)rl * 2 * c + 4 * q) = a;
+        *reinterpret_cast<float4*>(red + (size_t)rl * 2 * c + c + 4 * q) = b;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 2 * c; i += kThreads) {
+        float t = red[i];
+        for (int l = 1; l < lanes; ++l) t += red[(size_t)l * 2 * c + i];
+        part[(size_t)blockIdx.x * 2 * c + i] = t;
+    }
+}
+
+// bn_bwd_apply_kernel with relu and no residual, the mask from (scale, shift)
+__global__ __launch_bounds__(kThreads) void bn_bwd_apply_pre_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                    const float* __restrict__ scale,
+                                                                    const float* __restrict__ shift,
+                                                                    const float* __restrict__ mean,
+                                                                    const float* __restrict__ rstd,
+                                                                    const float* __restrict__ gamma,
+                                                                    const float* __restrict__ sums /*[2][c]*/, float inv_m,
+                                                                    int64_t total_quads, int quads, float* __restrict__ dx) {
+    const int c = quads * 4;
+    for (int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x; t < total_quads; t += (int64_t)gridDim.x * kThreads) {
+        const int q = (int)(t % quads);
+        const float4 xv = reinterpret_cast<const float4*>(x)[t];
+        const float4 sc = *reinterpret_cast<const float4*>(scale + 4 * q);
+        const float4 sh = *reinterpret_cast<const float4*>(shift + 4 * q);
+        const float4 g = relu_mask_pre(reinterpret_cast<const float4*>(dy)[t], xv, sc, sh);
+        const float4 mu = *reinterpret_cast<const float4*>(mean + 4 * q);
+        const float4 rs = *reinterpret_cast<const float4*>(rstd + 4 * q);
+        const float4 ga = *reinterpret_cast<const float4*>(gamma + 4 * q);
+        const float4 s1 = *reinterpret_cast<const float4*>(sums + 4 * q);
+        const float4 s2 = *reinterpret_cast<const float4*>(sums + c + 4 * q);
+        float4 o;
+        o.x = ga.x * rs.x * (g.x - s1.x * inv_m - (xv.x - mu.x) * rs.x * s2.x * inv_m);
+        o.y = ga.y * rs.y * (g.y - s1.y * inv_m - (xv.y - mu.y) * rs.y * s2.y * inv_m);
+        o.z = ga.z * rs.z * (g.z - s1.z * inv_m - (xv.z - mu.z) * rs.z * s2.z * inv_m);
+        o.w = ga.w * rs.w * (g.w - s1.w * inv_m - (xv.w - mu.w) * rs.w * s2.w * inv_m);
+        reinterpret_cast<float4*>(dx)[t] = o;
+    }
+}
+
 // batch statistics -> everything the forward / backward passes and the running buffers need: the block partials are
 // summed in a fixed order (32 channels x 32 block lanes per workgroup), then one thread per channel finishes
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ x, const float* __restrict__ part,
@@ -570,6 +646,27 @@ int seg3d_batchnorm_bwd(const float* dy, const float* y, const float* x, const f
     const int64_t tq = m * (c / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for(tq, kThreads * 4)), dim3(kThreads), 0, st, dy, y, x, mean, rstd,
                        gamma, sums, relu, 1.0f / (float)m, nullptr, tq, c / 4, dx, dres);
+    SEG3D_CHECK_LAUNCH();
+    return SEG3D_OK;
+}
+
+// seg3d_batchnorm_bwd for relu = 1, no residual, without y: the mask comes from x * scale + shift (see relu_mask_pre)
+int seg3d_batchnorm_bwd_pre(const float* dy, const float* x, const float* scale, const float* shift, const float* mean,
+                            const float* rstd, const float* gamma, int64_t m, int32_t c, float* dx,
+                            float* sums /*[2][c] out: dbeta, dgamma*/, void* workspace, size_t workspace_bytes, void* stream) {
+    if (m <= 0 || bad_c(c) || !sums) return SEG3D_EINVAL;
+    if (!workspace || workspace_bytes < seg3d_batchnorm_workspace_bytes(m, c)) return SEG3D_EWORKSPACE;
+    if (!dy || !x || !scale || !shift || !mean || !rstd || !gamma || !dx) return SEG3D_EINVAL;
+    hipStream_t st = as_stream(stream);
+    float* part = static_cast<float*>(workspace);
+    const unsigned nb = col_blocks(m, c);
+    hipLaunchKernelGGL(col_reduce_pre_kernel, dim3(nb), dim3(kThreads), kColSmem, st, x, dy, scale, shift, mean, rstd, m, c, part);
+    SEG3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(col_sums_finish, dim3((unsigned)((2 * c + 31) / 32)), dim3(1024), 0, st, part, (int)nb, c, sums);
+    SEG3D_CHECK_LAUNCH();
+    const int64_t tq = m * (c / 4);
+    hipLaunchKernelGGL(bn_bwd_apply_pre_kernel, dim3(blocks_for(tq, kThreads * 4)), dim3(kThreads), 0, st, dy, x, scale, shift,
+                       mean, rstd, gamma, sums, 1.0f / (float)m, tq, c / 4, dx);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }

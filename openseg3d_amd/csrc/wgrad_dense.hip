@@ -118,11 +118,17 @@ Plan plan(int64_t m, int cin, int cout, bool allow_lds = false) {
 // DEPTH (round 5, fp32 rows, split-K form): steps of a wave in flight.  The kernel is bound by its waves' round trips (~3 us per
 // 16 KB step at two waves per SIMD, section 6); a second register set does not fit 256 registers (101 - 223 spills), so the deep
 // form runs ONE wave per SIMD with DEPTH sets of x and dy rows (512 registers).
-template <bool XB, bool GROUP, int DEPTH = 1>
+// BN (seg3d_linear_wgrad_partials_bnrelu; fp32 rows, split-K form): x_v is the PRE-activation of a training-mode
+// BatchNorm1d + ReLU and the operand is max(x * scale_in + shift_in, 0), formed in make_b as the separate affine pass rounds
+// it.  A lane owns channels 4 cq .. + 3 for the whole kernel: eight more registers.
+template <bool XB, bool GROUP, int DEPTH = 1, bool BN = false>
 __global__ __launch_bounds__(kThreads, (DEPTH > 1 ? 1 : 2)) void wgrad_dense_kernel(const void* __restrict__ x_v, const float* __restrict__ dy,
                                                                int64_t m_rows, int cin, int cout, int rows_per_chunk,
                                                                int nbi, int tiles, float* __restrict__ part,
-                                                               int want_bias, int group) {
+                                                               int want_bias, int group,
+                                                               const float* __restrict__ scale_in,
+                                                               const float* __restrict__ shift_in) {
+    static_assert(!BN || (!XB && !GROUP && DEPTH == 1), "the BatchNorm + ReLU prologue is the fp32 split-K form's");
     const float* x = static_cast<const float*>(x_v);
     __shared__ __attribute__((aligned(16))) float red[GROUP ? 4 : 64 * 64];  // block sum [co_local][ci_local]
     __shared__ float red_b[GROUP ? 1 : kWaves][64];
@@ -147,6 +153,17 @@ __global__ __launch_bounds__(kThreads, (DEPTH > 1 ? 1 : 2)) void wgrad_dense_ker
     const uint32_t yoff = (uint32_t)((8 * rg * cout + (a_ok ? co0 + 4 * cq : 0)) * 4);
     const uint32_t xoff = (uint32_t)((8 * rg * cin + (b_ok ? ci0 + 4 * cq : 0)) * (XB ? 2 : 4));
     const bool want_db = want_bias && bi == 0;
+    f32x4 s_in = {0.f, 0.f, 0.f, 0.f}, t_in = s_in;  // BN: the affine of the lane's four channels
+    if constexpr (BN) {
+        s_in = *reinterpret_cast<const f32x4*>(scale_in + (b_ok ? ci0 + 4 * cq : 0));
+        t_in = *reinterpret_cast<const f32x4*>(shift_in + (b_ok ? ci0 + 4 * cq : 0));
+    }
+    auto bn_relu = [&](f32x4 v) {  // (-ffp-contract=off: a multiply, an add and a max per element)
+        v = v * s_in + t_in;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        return v;
+    };
 
     f32x4 acc[4][4];
 #pragma unroll
@@ -175,7 +192,8 @@ __global__ __launch_bounds__(kThreads, (DEPTH > 1 ? 1 : 2)) void wgrad_dense_ker
             for (int i = 0; i < 8; ++i) xs[i] = *reinterpret_cast<const f32x4*>(base + (size_t)i * cin * 4 + xoff);
         }
     };
-    auto make_b = [&](auto& xs) {
+    // activated: xs already holds the activation (BN: the partial step, which masks its padded rows AFTER the transform)
+    auto make_b = [&](auto& xs, auto activated) {
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             if constexpr (XB) {
@@ -183,11 +201,15 @@ __global__ __launch_bounds__(kThreads, (DEPTH > 1 ? 1 : 2)) void wgrad_dense_ker
             } else {
                 float v[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) v[i] = xs[i][b];
+                for (int i = 0; i < 8; ++i) {
+                    v[i] = xs[i][b];
+                    if constexpr (BN && !decltype(activated)::value) v[i] = fmaxf(v[i] * s_in[b] + t_in[b], 0.f);
+                }
                 split_frag(v, &b_hi[b], &b_lo[b]);
             }
         }
     };
+    constexpr std::false_type kRaw{};
     auto multiply = [&](auto& ys) {
         if (want_db) {
 #pragma unroll
@@ -226,7 +248,7 @@ __global__ __launch_bounds__(kThreads, (DEPTH > 1 ? 1 : 2)) void wgrad_dense_ker
                 const int cur = s + d * kStride;
                 if (cur < n_full) {  // (wave-uniform)
                     const bool more = cur + DEPTH * kStride < n_full;
-                    make_b(xd[d]);
+                    make_b(xd[d], kRaw);
                     if (more) load_x(cur + DEPTH * kStride, xd[d]);
                     multiply(yd[d]);
                     if (more) load_rows(dy, cout, yoff, cur + DEPTH * kStride, yd[d]);
@@ -240,7 +262,7 @@ __global__ __launch_bounds__(kThreads, (DEPTH > 1 ? 1 : 2)) void wgrad_dense_ker
         }
         for (; s < n_full; s += kStride) {
             const bool more = s + kStride < n_full;
-            make_b(xr);
+            make_b(xr, kRaw);
             if (more) load_x(s + kStride, xr);
             multiply(yr);
             if (more) load_rows(dy, cout, yoff, s + kStride, yr);
@@ -260,11 +282,13 @@ __global__ __launch_bounds__(kThreads, (DEPTH > 1 ? 1 : 2)) void wgrad_dense_ker
                 xq[i] = ok ? vx : make_uint2(0u, 0u);
             } else {
                 const f32x4 vx = *reinterpret_cast<const f32x4*>(x + r * cin + (b_ok ? ci0 + 4 * cq : 0));
-                xr[i] = ok ? vx : z;
+                // BN: max(0 * s + t, 0) is not zero -- a padded row is zeroed after the transform
+                if constexpr (BN) xr[i] = ok ? bn_relu(vx) : z;
+                else xr[i] = ok ? vx : z;
             }
             yr[i] = ok ? vy : z;
         }
-        make_b(xr);
+        make_b(xr, std::bool_constant<BN>{});
         multiply(yr);
     }
 
@@ -433,10 +457,10 @@ static void launch_dense(const Plan& p, const void* x, bool x_bf16, const float*
         const unsigned blocks = (unsigned)((p.chunks + 7) / 8 * 8) * (unsigned)groups;
         if (x_bf16)
             hipLaunchKernelGGL((wgrad_dense_kernel<true, true>), dim3(blocks), dim3(kThreads), 0, st, x, dy, m, cin, cout, (int)p.rows,
-                               nbi_g, groups, part, want_bias, p.group);
+                               nbi_g, groups, part, want_bias, p.group, nullptr, nullptr);
         else
             hipLaunchKernelGGL((wgrad_dense_kernel<false, true>), dim3(blocks), dim3(kThreads), 0, st, x, dy, m, cin, cout, (int)p.rows,
-                               nbi_g, groups, part, want_bias, p.group);
+                               nbi_g, groups, part, want_bias, p.group, nullptr, nullptr);
         return;
     }
     const int tiles = p.nbo * p.nbi;
@@ -452,15 +476,15 @@ static void launch_dense(const Plan& p, const void* x, bool x_bf16, const float*
     }();
     if (!x_bf16 && depth == 3) {
         hipLaunchKernelGGL((wgrad_dense_kernel<false, false, 3>), dim3(blocks), dim3(kThreads), 0, st, x, dy, m, cin, cout, (int)p.rows,
-                           p.nbi, tiles, part, want_bias, 0);
+                           p.nbi, tiles, part, want_bias, 0, nullptr, nullptr);
         return;
     }
     if (x_bf16)
         hipLaunchKernelGGL((wgrad_dense_kernel<true, false>), dim3(blocks), dim3(kThreads), 0, st, x, dy, m, cin, cout, (int)p.rows,
-                           p.nbi, tiles, part, want_bias, 0);
+                           p.nbi, tiles, part, want_bias, 0, nullptr, nullptr);
     else
         hipLaunchKernelGGL((wgrad_dense_kernel<false, false>), dim3(blocks), dim3(kThreads), 0, st, x, dy, m, cin, cout, (int)p.rows,
-                           p.nbi, tiles, part, want_bias, 0);
+                           p.nbi, tiles, part, want_bias, 0, nullptr, nullptr);
 }
 
 static int linear_wgrad_partials(const void* x, bool x_bf16, const float* dy, int64_t m, int32_t cin, int32_t cout,
@@ -481,6 +505,36 @@ extern "C" int seg3d_linear_wgrad_partials(const float* x, const float* dy, int6
                                            int32_t with_bias, void* workspace, size_t workspace_bytes, int32_t* chunks,
                                            void* stream) {
     return linear_wgrad_partials(x, false, dy, m, cin, cout, with_bias, workspace, workspace_bytes, chunks, stream);
+}
+
+// ... with x = max(x_pre * scale_in + shift_in, 0) formed on load (the training-mode BatchNorm1d + ReLU in front of the
+// Linear): the split-K kernel only, with the plan the plain entry would take for fp32 rows -- same chunks, same summation
+// order, the same bits as seg3d_affine_act + seg3d_linear_wgrad_partials.  Shapes that plan hands to another kernel (the
+// LDS-shared or the grouped form, both A/B switches) are refused: seg3d_linear_wgrad_bnrelu_fits tells.
+extern "C" int seg3d_linear_wgrad_bnrelu_fits(int64_t m, int32_t cin, int32_t cout) {
+    if (m <= 0 || cin <= 0 || cout <= 0 || (cin & 3) || (cout & 3)) return 0;
+    const Plan p = plan(m, cin, cout, true);
+    return !p.lds && !p.group;
+}
+
+extern "C" int seg3d_linear_wgrad_partials_bnrelu(const float* x_pre, const float* scale_in, const float* shift_in,
+                                                  const float* dy, int64_t m, int32_t cin, int32_t cout, int32_t with_bias,
+                                                  void* workspace, size_t workspace_bytes, int32_t* chunks, void* stream) {
+    if (m < 0 || cin <= 0 || cout <= 0 || (cin & 3) || (cout & 3) || !chunks) return SEG3D_EINVAL;
+    if (m > 0 && (!x_pre || !scale_in || !shift_in || !dy)) return SEG3D_EINVAL;
+    if (workspace_bytes < seg3d_linear_wgrad_workspace_bytes(m, cin, cout) || (m > 0 && !workspace)) return SEG3D_EINVAL;
+    *chunks = 0;
+    if (m == 0) return SEG3D_OK;
+    const Plan p = plan(m, cin, cout, true);
+    if (p.lds || p.group) return SEG3D_EINVAL;
+    const int tiles = p.nbo * p.nbi;
+    const unsigned blocks = (unsigned)((p.chunks + 7) / 8 * 8) * (unsigned)tiles;
+    hipLaunchKernelGGL((wgrad_dense_kernel<false, false, 1, true>), dim3(blocks), dim3(kThreads), 0, as_stream(stream), x_pre, dy,
+                       m, cin, cout, (int)p.rows, p.nbi, tiles, static_cast<float*>(workspace), with_bias ? 1 : 0, 0, scale_in,
+                       shift_in);
+    SEG3D_CHECK_LAUNCH();
+    *chunks = p.chunks;
+    return SEG3D_OK;
 }
 
 extern "C" int seg3d_linear_wgrad_partials_xbf16(const uint16_t* x_bf16, const float* dy, int64_t m, int32_t cin, int32_t cout,

@@ -1251,14 +1251,24 @@ class _BatchNormActFn(torch.autograd.Function):
         y = torch.empty_like(x)
         r = None if res is None else _f32c(res)
         _lib.call("seg3d_affine_act", _ptr(x), _ptr(r), _ptr(scale), _ptr(shift), int(relu), m, c, _ptr(y), _stream())
-        ctx.save_for_backward(x, y, mean, rstd, gamma)
+        # ReLU without a residual: the backward forms the mask from x * scale + shift again (bit for bit the sign of y,
+        # seg3d_batchnorm_bwd_pre) and y is not kept
+        ctx.pre = bool(relu) and res is None
+        if ctx.pre:
+            ctx.save_for_backward(x, scale, shift, mean, rstd, gamma)
+        else:
+            ctx.save_for_backward(x, y, mean, rstd, gamma)
         ctx.relu, ctx.has_res = relu, res is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, mean, rstd, gamma = ctx.saved_tensors
         dy = _f32c(dy)
+        if ctx.pre:
+            x, scale, shift, mean, rstd, gamma = ctx.saved_tensors
+            dx, sums = _batchnorm_bwd_pre(dy, x, scale, shift, mean, rstd, gamma)
+            return dx, None, sums[1], sums[0], None, None, None, None, None
+        x, y, mean, rstd, gamma = ctx.saved_tensors
         m, c = x.shape
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if ctx.has_res else None
@@ -1268,6 +1278,18 @@ class _BatchNormActFn(torch.autograd.Function):
         _lib.call("seg3d_batchnorm_bwd", _ptr(dy), _ptr(y), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), int(ctx.relu),
                   m, c, _ptr(dx), _ptr(dres), _ptr(sums), _ptr(ws), ws_bytes, _stream())
         return dx, dres, sums[1], sums[0], None, None, None, None, None
+
+
+def _batchnorm_bwd_pre(dy, x, scale, shift, mean, rstd, gamma):
+    """(dx, sums = [dbeta, dgamma]) of BatchNorm1d + ReLU (no residual) from the pre-activation x and the folded affine."""
+    m, c = x.shape
+    dx = torch.empty_like(x)
+    sums = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    ws_bytes = _lib.query("seg3d_batchnorm_workspace_bytes", m, c)
+    ws = _workspace(ws_bytes, x.device)
+    _lib.call("seg3d_batchnorm_bwd_pre", _ptr(dy), _ptr(x), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(rstd), _ptr(gamma),
+              m, c, _ptr(dx), _ptr(sums), _ptr(ws), ws_bytes, _stream())
+    return dx, sums
 
 
 # ---- torch.nn.SyncBatchNorm (tools/train.py:246-247, --sync_bn): statistics over the rows of ALL ranks
@@ -1494,6 +1516,106 @@ def bn_eval_affine(bn):
     return cached[1], cached[2], key
 
 
+def _bn_batch_stats(xc, bn):
+    """stats [6, c] of seg3d_batchnorm_stats for the rows xc (row 2 mean, 3 rstd, 4 scale, 5 shift): batch statistics,
+    folded affine and the running buffers' update in one call (two small launches)."""
+    m, c = xc.shape
+    with torch.no_grad():
+        stats = torch.empty((6, c), dtype=torch.float32, device=xc.device)
+        track = bn.training and bn.track_running_stats
+        mom = 0.0
+        if track:
+            # the kernel updates the running buffers through raw pointers: tell the eval-affine cache
+            bn._seg3d_stats_epoch = getattr(bn, "_seg3d_stats_epoch", 0) + 1
+            _bump_batches_tracked(bn)
+            mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+        ws_bytes = _lib.query("seg3d_batchnorm_workspace_bytes", m, c)
+        ws = _workspace(ws_bytes, xc.device)
+        _lib.call("seg3d_batchnorm_stats", _ptr(xc), m, c, float(bn.eps), _ptr(bn.weight), _ptr(bn.bias), float(mom),
+                  _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None, _ptr(stats),
+                  _ptr(ws), ws_bytes, _stream())
+    return stats
+
+
+# Per-point MLPs in training: a hidden layer's BatchNorm1d + ReLU output z = max(y * scale + shift, 0) is a pure function
+# of the pre-activation y and two per-column vectors, and at 174 633 x 256 it is the largest tensor of the model.  With
+# POINT_BN_ONLOAD the next Linear and its weight gradient form z in registers from the y they load instead
+# (seg3d_linear_fwd_x6_bnrelu, seg3d_linear_wgrad_partials_bnrelu) and the BatchNorm backward takes the ReLU mask from y
+# (seg3d_batchnorm_bwd_pre): z is never written, read or kept.  Same arithmetic in the same order -- the step is
+# bit-identical to the composed path.  SEG3D_POINT_BN_ONLOAD=0 (or ops.POINT_BN_ONLOAD = False at run time) turns it off.
+POINT_BN_ONLOAD = os.environ.get("SEG3D_POINT_BN_ONLOAD", "1") != "0"
+
+
+class _BnReluLinearFn(torch.autograd.Function):
+    """y = max(x_pre * scale + shift, 0) W^T (+ b): training-mode BatchNorm1d + ReLU + exact Linear as one node; the
+    statistics (mean, rstd, scale, shift) are computed by the caller."""
+
+    @staticmethod
+    def forward(ctx, x_pre, gamma, beta, weight, bias, mean, rstd, scale, shift):
+        cout, cin = weight.shape
+        y = torch.empty((x_pre.shape[0], cout), dtype=torch.float32, device=x_pre.device)
+        _lib.call("seg3d_linear_fwd_x6_bnrelu", _ptr(x_pre), _ptr(scale), _ptr(shift), x_pre.shape[0],
+                  _ptr(_linear_pack_x6(weight)), _ptr(None if bias is None else _f32c(bias)), cin, cout, _ptr(y), _stream())
+        ctx.save_for_backward(x_pre, mean, rstd, scale, shift, gamma, weight)
+        ctx.has_bias = bias is not None
+        ctx.bias_param = bias  # (a reference for the deferred-join bookkeeping of the weight-gradient stream)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x_pre, mean, rstd, scale, shift, gamma, weight = ctx.saved_tensors
+        dy = _f32c(dy)
+        cout, cin = weight.shape
+        m = x_pre.shape[0]
+        dx = dgamma = dbeta = dw = db = None
+        fk = _WgradFork(dy.device)
+        want_db = ctx.has_bias and ctx.needs_input_grad[4]
+        if ctx.needs_input_grad[3]:  # on the side stream, co-running with the input gradient below
+            dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+            if want_db:
+                db = torch.empty((cout,), dtype=torch.float32, device=dy.device)
+            ws_bytes = _lib.query("seg3d_linear_wgrad_workspace_bytes", m, cin, cout)
+            ws = _workspace(ws_bytes, dy.device)
+            chunks = ctypes.c_int32(0)
+            _lib.call("seg3d_linear_wgrad_partials_bnrelu", _ptr(x_pre), _ptr(scale), _ptr(shift), _ptr(dy), m, cin, cout,
+                      1 if want_db else 0, _ptr(ws), ws_bytes, ctypes.byref(chunks), fk.fork(ws, x_pre, scale, dy))
+            fk.add_reduce(ws, chunks.value, cin * cout + cout, cin * cout, dw.data_ptr(), db.data_ptr() if want_db else 0)
+        elif want_db:
+            db = dy.sum(0)
+        if any(ctx.needs_input_grad[:3]):
+            dz = _linear_apply(dy, _linear_pack(weight, 1), None, cout, cin)
+            dx, sums = _batchnorm_bwd_pre(dz, x_pre, scale, shift, mean, rstd, gamma)
+            dgamma, dbeta = sums[1], sums[0]
+        fk.join((weight, dw), (ctx.bias_param, db))
+        return dx, dgamma, dbeta, dw, db, None, None, None, None
+
+
+def bn_relu_linear_fits(x, bn, lin):
+    """Whether ops.bn_relu_linear takes (BatchNorm1d bn, ReLU, Linear lin) on the rows x: training with gradients, a
+    BatchNorm on batch_norm_act's fast path with no SyncBatchNorm group, a Linear on the six-product kernel whose weight
+    gradient takes the split-K kernel, fp32 training copies."""
+    if not (POINT_BN_ONLOAD and torch.is_grad_enabled() and bn.training and bn.track_running_stats and bn.affine):
+        return False
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.shape[0] >= 2):
+        return False
+    cout, cin = lin.weight.shape
+    if bn.num_features != cin or cin != x.shape[1] or cin > 1024 or not _x6_fits(cin, cout):
+        return False
+    if not (CONV_PRECISION == "bf16x3" and TRAIN_STORAGE == "fp32") or _sync_bn_group(bn) is not None:
+        return False
+    return bool(_lib.query("seg3d_linear_wgrad_bnrelu_fits", x.shape[0], cin, cout))
+
+
+def bn_relu_linear(x_pre, bn, lin):
+    """lin(relu(bn(x_pre))) for a training-mode BatchNorm1d and an exact Linear (the hidden layers of the per-point MLPs)
+    without the activated tensor: bit-identical to batch_norm_act(x_pre, bn, relu=True) followed by
+    linear(., lin.weight, lin.bias, exact=True), outputs, gradients and running buffers.  The caller checks
+    bn_relu_linear_fits."""
+    xc = _f32c(x_pre)
+    stats = _bn_batch_stats(xc, bn)
+    return _BnReluLinearFn.apply(xc, bn.weight, bn.bias, lin.weight, lin.bias, stats[2], stats[3], stats[4], stats[5])
+
+
 def batch_norm_act(x, bn, relu=True, res=None):
     """act(bn(x) (+ res)) for an nn.BatchNorm1d over [rows, C] features (C % 4 == 0), relu optional.
     Training: batch statistics (biased variance for the normalisation, unbiased into running_var, as torch);
@@ -1512,21 +1634,7 @@ def batch_norm_act(x, bn, relu=True, res=None):
         return torch.relu(y) if relu else y
     if use_batch:
         xc = _f32c(x)
-        m = xc.shape[0]
-        with torch.no_grad():  # statistics, folded affine and running buffers in one call (two small launches)
-            stats = torch.empty((6, c), dtype=torch.float32, device=x.device)
-            track = bn.training and bn.track_running_stats
-            mom = 0.0
-            if track:
-                # the kernel updates the running buffers through raw pointers: tell the eval-affine cache
-                bn._seg3d_stats_epoch = getattr(bn, "_seg3d_stats_epoch", 0) + 1
-                _bump_batches_tracked(bn)
-                mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-            ws_bytes = _lib.query("seg3d_batchnorm_workspace_bytes", m, c)
-            ws = _workspace(ws_bytes, x.device)
-            _lib.call("seg3d_batchnorm_stats", _ptr(xc), m, c, float(bn.eps), _ptr(bn.weight), _ptr(bn.bias), float(mom),
-                      _ptr(bn.running_mean) if track else None, _ptr(bn.running_var) if track else None, _ptr(stats),
-                      _ptr(ws), ws_bytes, _stream())
+        stats = _bn_batch_stats(xc, bn)
         return _BatchNormActFn.apply(xc, res, bn.weight, bn.bias, stats[2], stats[3], stats[4], stats[5], bool(relu))
     with torch.no_grad():
         # eval: the folded affine is a constant of the module; keyed on the tensors' versions so that loading a checkpoint

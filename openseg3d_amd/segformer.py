@@ -82,6 +82,12 @@ class FusedMLP(nn.Sequential):
             if isinstance(m, (nn.BatchNorm1d, nn.SyncBatchNorm)) and not isinstance(m, NarrowBatchNorm1d) \
                     and m.num_features % 4 == 0:
                 relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                # training: BatchNorm1d -> ReLU -> Linear without the activated tensor (formed on the Linear's operand load)
+                if relu and self.training and i + 2 < len(mods) and isinstance(mods[i + 2], RowLinear) \
+                        and ops.bn_relu_linear_fits(x, m, mods[i + 2]):
+                    x = ops.bn_relu_linear(x, m, mods[i + 2])
+                    i += 3
+                    continue
                 x = ops.batch_norm_act(x, m, relu=relu)
                 i += 2 if relu else 1
             else:

@@ -1,8 +1,9 @@
 """Per-kernel totals inside the training steps of a `rocprofv3 --kernel-trace --output-format csv` run of bench.py.
 
-usage: python tools/trace_summary.py <kernel_trace.csv> [--steps N] [--csv out.csv] [--top 60]
+usage: python tools/trace_summary.py <kernel_trace.csv> [--steps N] [--csv out.csv] [--queue-csv out.csv] [--top 60]
        python tools/trace_summary.py --criterion <kernel_trace.csv[.gz]> [--steps N] [--csv out.csv]
 Training steps are delimited by the optimizer's launches (fused SGD): the last N of them bound N steps.
+--queue-csv writes the steps' kernels per queue (main = the optimizer's) in the columns of the --criterion table.
 --criterion cuts the criterion interval of every step instead (criterion_interval below)."""
 import argparse
 import collections
@@ -38,6 +39,7 @@ def main():
     ap.add_argument("trace")
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--csv")
+    ap.add_argument("--queue-csv", help="kernel,queue,launches_per_step,us_per_step,us_per_launch of the training steps")
     ap.add_argument("--top", type=int, default=60)
     ap.add_argument("--criterion", action="store_true", help="the criterion interval of every step (criterion_interval)")
     a = ap.parse_args()
@@ -46,7 +48,7 @@ def main():
     rows = []
     with open(a.trace) as f:
         for r in csv.DictReader(f):
-            rows.append((r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
+            rows.append((r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Queue_Id", "0")))
     rows.sort(key=lambda r: r[1])
     # the optimizer's own launches only: `_foreach_add_` on the BatchNorm step counters is a multi_tensor_apply kernel too
     opt = [i for i, r in enumerate(rows) if "FusedSgd" in r[0] or "fused_sgd" in r[0].lower()]
@@ -63,7 +65,7 @@ def main():
     span = (win[-1][2] - win[0][1]) / 1e6 / a.steps
     tot = collections.defaultdict(lambda: [0, 0])
     fam = collections.defaultdict(float)
-    for n, s, e in win:
+    for n, s, e, _ in win:
         k = short(n)
         tot[k][0] += 1
         tot[k][1] += e - s
@@ -82,6 +84,21 @@ def main():
             f.write("kernel,launches_per_step,ms_per_step,us_per_launch,share\n")
             for k, (c, ns) in out:
                 f.write(f"\"{k}\",{c / a.steps:.2f},{ns / 1e6 / a.steps:.4f},{ns / 1e3 / c:.2f},{ns / 1e6 / a.steps / busy:.4f}\n")
+
+
+    if a.queue_csv:
+        main_q = rows[last][3]
+        per = collections.defaultdict(lambda: [0, 0])
+        for n, s, e, q in win:
+            key = (short(n), "main" if q == main_q else "other")
+            per[key][0] += 1
+            per[key][1] += e - s
+        with open(a.queue_csv, "w") as f:
+            f.write("kernel,queue,launches_per_step,us_per_step,us_per_launch\n")
+            for (n, q), (cnt, ns) in sorted(per.items(), key=lambda kv: -kv[1][1]):
+                f.write(f"\"{n}\",{q},{cnt / a.steps:.2f},{ns / 1e3 / a.steps:.2f},{ns / 1e3 / cnt:.2f}\n")
+            f.write(f"\"# wall_us per step\",,,{span * 1e3:.2f},\n")
+            f.write(f"\"# busy_us per step (sum over kernels)\",,,{busy * 1e3:.2f},\n")
 
 
 def criterion_interval(trace, steps, out_csv):
