@@ -509,6 +509,12 @@ int seg3d_layernorm_bwd_partials(const float* dy, const float* x, const float* m
 size_t seg3d_batchnorm_workspace_bytes(int64_t m, int32_t c);
 int seg3d_colstats(const float* x, int64_t m, int32_t c, float* sums, void* workspace, size_t workspace_bytes,
                    void* stream);
+/* seg3d_colstats about a shift [c] of the caller's instead of x[0] (NULL = x[0]): sums[0..c) = sum_r (x - shift),
+ * sums[c..2c) = sum_r (x - shift)^2.  The relative error of the variance formed from them grows with
+ * 1 + ((shift - mean) / sigma)^2, so a shift near the column mean (the mean of a few rows) keeps it at rounding level
+ * whatever row 0 holds; SyncBatchNorm's per-rank moments use it. */
+int seg3d_colstats_about(const float* x, const float* shift, int64_t m, int32_t c, float* sums, void* workspace,
+                         size_t workspace_bytes, void* stream);
 int seg3d_batchnorm_stats(const float* x, int64_t m, int32_t c, float eps, const float* gamma, const float* beta,
                           float momentum, float* running_mean, float* running_var, float* stats, void* workspace,
                           size_t workspace_bytes, void* stream);

@@ -209,6 +209,8 @@ __global__ __launch_bounds__(1024) void ln_bwd_reduce(const float* __restrict__ 
 // ------------------------------------------------------------------ column reductions / affine passes (BatchNorm)
 // thread -> (channel quad q = t % quads, row lane = t / quads); rows advance by the number of row lanes.
 // MODE 0: sums of (x - x0), (x - x0)^2 with x0 = row 0 (shifted sums: no cancellation in the variance)
+// MODE 2: the same sums about a shift [c] that the caller hands in through `mean` (the error of the variance grows with
+//         1 + ((shift - mean) / sigma)^2: a caller that cannot live with row 0's luck brings an estimate of the mean)
 // MODE 1: sums of g, g * xhat with g = dy masked by (y > 0) when relu, xhat = (x - mean) * rstd
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void col_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
@@ -223,13 +225,14 @@ __global__ __launch_bounds__(kThreads) void col_reduce_kernel(const float* __res
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
         float4 p0 = a, p1 = a;
         if (MODE == 0) p0 = *reinterpret_cast<const float4*>(x + 4 * q);  // shift
+        if (MODE == 2) p0 = *reinterpret_cast<const float4*>(mean + 4 * q);
         if (MODE == 1) {
             p0 = *reinterpret_cast<const float4*>(mean + 4 * q);
             p1 = *reinterpret_cast<const float4*>(rstd + 4 * q);
         }
         for (int64_t row = (int64_t)blockIdx.x * lanes + rl; row < m; row += (int64_t)gridDim.x * lanes) {
             const float4 xv = *reinterpret_cast<const float4*>(x + row * c + 4 * q);
-            if (MODE == 0) {
+            if (MODE != 1) {
                 const float dx_ = xv.x - p0.x, dy_ = xv.y - p0.y, dz_ = xv.z - p0.z, dw_ = xv.w - p0.w;
                 a.x += dx_; a.y += dy_; a.z += dz_; a.w += dw_;
                 b.x += dx_ * dx_; b.y += dy_ * dy_; b.z += dz_ * dz_; b.w += dw_ * dw_;
@@ -584,6 +587,23 @@ int seg3d_colstats(const float* x, int64_t m, int32_t c, float* sums /*[2][c]: s
     float* part = static_cast<float*>(workspace);
     const unsigned nb = col_blocks(m, c);
     hipLaunchKernelGGL(col_reduce_kernel<0>, dim3(nb), dim3(kThreads), kColSmem, st, x, nullptr, nullptr, nullptr, nullptr, 0, m,
+                       c, part);
+    SEG3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(col_sums_finish, dim3((unsigned)((2 * c + 31) / 32)), dim3(1024), 0, st, part, (int)nb, c, sums);
+    SEG3D_CHECK_LAUNCH();
+    return SEG3D_OK;
+}
+
+// seg3d_colstats about a shift [c] of the caller's instead of row 0 (NULL = row 0)
+int seg3d_colstats_about(const float* x, const float* shift, int64_t m, int32_t c, float* sums, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!shift) return seg3d_colstats(x, m, c, sums, workspace, workspace_bytes, stream);
+    if (m <= 0 || bad_c(c) || !sums || !x) return SEG3D_EINVAL;
+    if (!workspace || workspace_bytes < seg3d_batchnorm_workspace_bytes(m, c)) return SEG3D_EWORKSPACE;
+    hipStream_t st = as_stream(stream);
+    float* part = static_cast<float*>(workspace);
+    const unsigned nb = col_blocks(m, c);
+    hipLaunchKernelGGL(col_reduce_kernel<2>, dim3(nb), dim3(kThreads), kColSmem, st, x, nullptr, nullptr, shift, nullptr, 0, m,
                        c, part);
     SEG3D_CHECK_LAUNCH();
     hipLaunchKernelGGL(col_sums_finish, dim3((unsigned)((2 * c + 31) / 32)), dim3(1024), 0, st, part, (int)nb, c, sums);
