@@ -10,38 +10,7 @@
 // SEG3D_EINVAL; seg3d_window_attn_supported says so up front.  The round-1 / round-2 fallbacks (prepare pass + core,
 // three-launch backward with prepared operands through HBM, vector-ALU forward) were removed in round 3: nothing on the
 // reference's path reached them and their workspace demand (gigabytes on a 2 M-point scene) leaked into every call.
-#include <cstdlib>
-
 #include "attn_common.hpp"
-#include "attn_dropout.hpp"
-
-bool attn_fused_supported(int heads, int dh);  // attention_fused.hip
-int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles,
-                          const int32_t* chunk_item, int n_chunks, int heads, int dh, const float* tau, float tau_min,
-                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st);
-int attn_fused_fwd_schedule(int n_tiles, int n_chunks, int heads, int dh, bool dropout, int* cap, int* grid, int* walked,
-                            int* xb);
-size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh);  // attention_fused_bwd.hip
-size_t attn_fused_bwd_workspace_bytes(int64_t m, int n_tiles, int n_chunks, int heads, int dh);  // attention_fused_bwd.hip
-bool attn_fused_bwd_supported(int heads, int dh);
-int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
-                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
-                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, const int32_t* chunk_item,
-                          int n_chunks, int64_t m, int heads, int dh, const float* tau, float tau_min, float* dq, float* dk,
-                          float* dv, int lddq, int lddk, int lddv, float* dtau, void* workspace, const DropoutParams& drop,
-                          hipStream_t st);
-bool attn_small_supported(int heads, int dh);  // attention_small.hip
-size_t attn_small_blocks(int n_tiles);
-int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads,
-                          int dh, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-                          hipStream_t st);
-int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
-                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
-                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads, int dh,
-                          const float* tau, float tau_min, float* dq, float* dk, float* dv, int lddq, int lddk, int lddv,
-                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st);
 
 namespace {
 
@@ -59,7 +28,7 @@ int bwd_path(int heads, int dh) {
 // never / with dropout (default) / always.  (The vector-ALU kernel always writes the LSE: a caller that passes none stays
 // on the fused one.)
 bool small_fwd_runs(int heads, int dh, float dropout_p, bool has_lse) {
-    static const int small_fwd = getenv("SEG3D_ATTN_SMALL_FWD") ? atoi(getenv("SEG3D_ATTN_SMALL_FWD")) : 1;
+    static const int small_fwd = env_int("SEG3D_ATTN_SMALL_FWD", 1);
     return (small_fwd == 2 || (small_fwd == 1 && dropout_p > 0.f)) && attn_small_supported(heads, dh) && has_lse;
 }
 

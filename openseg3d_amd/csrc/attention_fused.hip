@@ -590,8 +590,8 @@ FwdSchedule fwd_schedule(int n_tiles, int n_chunks, int heads, bool dropout) {
         }
         return cus;
     }();
-    static const int per_cu_env = getenv("SEG3D_ATTN_WGS_PER_CU") ? atoi(getenv("SEG3D_ATTN_WGS_PER_CU")) : 0;  // A/B
-    static const int xcd_env = getenv("SEG3D_ATTN_XCD") ? atoi(getenv("SEG3D_ATTN_XCD")) : 8;  // A/B: 1 = flat order
+    static const int per_cu_env = env_int("SEG3D_ATTN_WGS_PER_CU", 0);  // A/B
+    static const int xcd_env = env_int("SEG3D_ATTN_XCD", 8);            // A/B: 1 = flat order
     FwdSchedule s;
     s.n_items = C::kNarrow ? n_tiles : n_chunks;
     s.hgn = heads / C::HG;

@@ -38,8 +38,6 @@ extern "C" int seg3d_debug_attn_bwd_stamps(void* buf) {
 #define BSTAMP(var) do {} while (0)
 #endif
 
-size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh);  // below: blocks of each pass
-
 namespace {
 
 using namespace attn;

@@ -13,10 +13,6 @@
 // with the gradient through x_hat = x / max(|x|, eps) applied to the thread's own vector at the end.
 // Work items are the (window, 32-token tile) list of seg3d_window_partition; block = 32 tokens x heads threads.
 #include "attn_common.hpp"
-#include "attn_dropout.hpp"
-
-size_t attn_small_blocks(int n_tiles);  // below: workgroups of every launch in this file
-bool attn_small_supported(int heads, int dh);
 
 namespace {
 

@@ -3,6 +3,41 @@
 #pragma once
 #include "split_bf16.hpp"
 
+#include "attn_dropout.hpp"  // after the HIP runtime's header: DropoutParams
+
+// The launchers and queries behind the entry points of attention.hip, declared once for the file that defines them and
+// for their callers.  n_chunks <= n_tiles; workspace sizes in bytes, block counts in workgroups.
+// attention_fused.hip
+bool attn_fused_supported(int heads, int dh);
+int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
+                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles,
+                          const int32_t* chunk_item, int n_chunks, int heads, int dh, const float* tau, float tau_min,
+                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st);
+int attn_fused_fwd_schedule(int n_tiles, int n_chunks, int heads, int dh, bool dropout, int* cap, int* grid, int* walked,
+                            int* xb);
+// attention_fused_bwd.hip
+bool attn_fused_bwd_supported(int heads, int dh);
+size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh);
+size_t attn_fused_bwd_workspace_bytes(int64_t m, int n_tiles, int n_chunks, int heads, int dh);
+int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
+                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
+                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, const int32_t* chunk_item,
+                          int n_chunks, int64_t m, int heads, int dh, const float* tau, float tau_min, float* dq, float* dk,
+                          float* dv, int lddq, int lddk, int lddv, float* dtau, void* workspace, const DropoutParams& drop,
+                          hipStream_t st);
+// attention_small.hip
+bool attn_small_supported(int heads, int dh);
+size_t attn_small_blocks(int n_tiles);
+int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
+                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads,
+                          int dh, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
+                          hipStream_t st);
+int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
+                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
+                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads, int dh,
+                          const float* tau, float tau_min, float* dq, float* dk, float* dv, int lddq, int lddk, int lddv,
+                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st);
+
 namespace attn {
 
 using namespace sbf;

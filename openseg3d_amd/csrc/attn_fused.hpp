@@ -1,9 +1,7 @@
 // Geometry and helpers shared by the fused window-attention kernels (attention_fused.hip: forward,
 // attention_fused_bwd.hip: the two backward passes).  See attention_fused.hip for the design.
 #pragma once
-#include <cstdlib>
 #include "attn_common.hpp"
-#include "attn_dropout.hpp"
 
 namespace attn_fused {
 
@@ -70,7 +68,7 @@ __host__ __device__ __forceinline__ int xcd_block_count(int n_items, int gx, int
 // training step a tie (43.0 ms) -- the kernels are not bound by the fabric, the traffic is what falls.  Lists of fewer than
 // 512 chunks (stage 4: 242) keep single items: blocks of 4 leave 60 blocks for 8 XCDs and cost that stage 5 %.
 inline int xcd_block_items(bool narrow, int n_items) {
-    static const int env = getenv("SEG3D_ATTN_XCD_BLOCK") ? atoi(getenv("SEG3D_ATTN_XCD_BLOCK")) : 0;
+    static const int env = env_int("SEG3D_ATTN_XCD_BLOCK", 0);
     return env > 0 ? env : (narrow ? 8 : (n_items >= 512 ? 4 : 1));
 }
 

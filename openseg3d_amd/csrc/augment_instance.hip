@@ -13,19 +13,15 @@
 // device memory (counts[0]); the host reads nothing until the whole chain is enqueued.  The lexicographic minimum and
 // the OR are exact and order-independent and the two means use one fixed summation order, so the result is a pure
 // function of the inputs; the host twin below shares every recipe and gives the same bits.  All arithmetic is double.
-#include <math.h>
 #include <string.h>
 
-#include <vector>
-
-#include "common.hpp"
+#include "instance_geom.hpp"
 
 // fixed sequences of IEEE products and sums, as numpy rounds them; no fused multiply-add (see augment.hip)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / SEG3D_WAVE;
 constexpr int kMaxDim = 16;
 constexpr int kMaxAngles = SEG3D_AUG_MAX_ANGLES;
@@ -38,7 +34,7 @@ struct GroundSet {
 
 // instance_augmentation.py:35-43: 0 = label 255 (skipped), 1 = ground, 2 = object
 __host__ __device__ __forceinline__ int row_kind(const GroundSet& g, const void* labels, int label_bytes, int64_t i) {
-    const int64_t l = label_bytes == 1 ? (int64_t) static_cast<const uint8_t*>(labels)[i] : static_cast<const int64_t*>(labels)[i];
+    const int64_t l = label_at(labels, label_bytes, i);
     if (l == 255) return 0;
     return (l >= 0 && l < 256 && g.is_ground[l]) ? 1 : 2;
 }
@@ -58,16 +54,7 @@ struct ScanRec {
     int32_t occ;   // 1: an object row within `radius`
 };
 
-// (distance, row) ordered lexicographically: np.argmin keeps the lowest index among equal distances (:149)
-__host__ __device__ __forceinline__ bool closer(double d, int32_t row, double bd, int32_t brow) {
-    return d < bd || (d == bd && row < brow);
-}
-
-// np.linalg.norm over three columns (:137, :144, :184): ((dx*dx + dy*dy) + dz*dz), IEEE sqrt
-__host__ __device__ __forceinline__ double dist3(double x, double y, double z, const double* c) {
-    const double dx = x - c[0], dy = y - c[1], dz = z - c[2];
-    return sqrt((dx * dx + dy * dy) + dz * dz);
-}
+// closer (np.argmin, :149) and dist3 (np.linalg.norm, :137, :144, :184) are instance_geom.hpp's
 
 // flip over the short axis (:63-64, :121-125): the 2 x 2 matrix of the axes through center0
 __host__ __device__ __forceinline__ void flip_matrix(const double* c0, double* m) {
@@ -128,33 +115,7 @@ __host__ __device__ __forceinline__ bool candidate_passes(const ScanRec& r, doub
 }
 
 // ------------------------------------------------------------------------------------------ device
-// The fixed summation order of the two means: thread t adds rows t, t + 256, ... in ascending order, then the 256
-// partial sums are folded by halving (t += t + 128, t += t + 64, ...).  sum3_host below does the same.
-__device__ void block_sum3(double* v, double* lds) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    for (int c = 0; c < 3; ++c) lds[c * kThreads + t] = v[c];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s)
-            for (int c = 0; c < 3; ++c) lds[c * kThreads + t] += lds[c * kThreads + t + s];
-        __syncthreads();
-    }
-    for (int c = 0; c < 3; ++c) v[c] = lds[c * kThreads];
-}
-
-__device__ double block_max(double v, double* lds) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    lds[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s && lds[t + s] > lds[t]) lds[t] = lds[t + s];
-        __syncthreads();
-    }
-    return lds[0];
-}
-
+// the two means are summed in the one order of block_sum3 (instance_geom.hpp)
 // :47-74 for one instance: transformed xyz -> xyz [m, 3], candidate centres / radius -> st
 __device__ void prepare_block(const seg3d_aug_instance_plan& p, const double* __restrict__ bank, int dim,
                               double* __restrict__ xyz, InstState* __restrict__ st, double* lds) {
@@ -425,14 +386,6 @@ int inst_launch(const T* pts, int64_t n, int dim, const void* labels, int label_
 }
 
 // ------------------------------------------------------------------------------------------ host twin
-void sum3_host(const std::vector<double>& part, double* v) {  // part [3][kThreads]: block_sum3's fold
-    std::vector<double> l(part);
-    for (int s = kThreads / 2; s > 0; s >>= 1)
-        for (int t = 0; t < s; ++t)
-            for (int c = 0; c < 3; ++c) l[c * kThreads + t] += l[c * kThreads + t + s];
-    for (int c = 0; c < 3; ++c) v[c] = l[c * kThreads];
-}
-
 void prepare_host(const seg3d_aug_instance_plan& p, const double* bank, int dim, double* xyz, InstState* st) {
     const int m = p.n_rows;
     const double* rows = bank + p.row_begin * dim;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/seg3d_hip.h"
 
@@ -28,6 +29,22 @@ void seg3d_note_hip_error(int code, const char* file, int line);
             return SEG3D_ELAUNCH;                                     \
         }                                                             \
     } while (0)
+
+// ---------------------------------------------------------------- A/B switches ("switches")
+// The only readers of the environment in csrc/.  The value is atoi's: unset gives the default, a set variable with no
+// leading number (empty too) reads as 0.  Callers keep the value in a `static const`: once per process.
+static inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+
+static inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// ... and the default for a value outside [lo, hi]
+static inline int env_int_in(const char* name, int lo, int hi, int dflt) {
+    const int v = env_int(name, dflt);
+    return (v >= lo && v <= hi) ? v : dflt;
+}
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -104,3 +121,32 @@ static inline size_t scan_tmp_count(int64_t n) { return (size_t)ceil_div64(n > 0
 int scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* total /*device, may be NULL*/,
                        uint32_t* tmp, hipStream_t st);
 int scan_exclusive_u32x4(const uint4* in, uint4* out, int64_t n, uint4* total, uint4* tmp, hipStream_t st);
+
+// ---------------------------------------------------------------- functions one .hip defines and another calls
+// Declared here once; the defining file includes this header too, so a changed signature fails to compile instead of
+// linking against a stale copy.  (The attention launchers are in attn_common.hpp.)
+// group.hip: the deterministic group index behind seg3d_group_index, with its count / offset arrays handed out (window.hip)
+int group_index_launch(const int32_t* gid, int64_t n, int64_t ng, int32_t* rank, int32_t* order, int32_t* offsets,
+                       void* workspace, hipStream_t st, uint32_t** count_out, uint32_t** offs_out);
+// spconv_split.hip: the split-bf16 gather-GEMM behind the entry points of spconv.hip
+size_t spconv_split_packed_bytes(int cin_op, int cout_op, int kk);
+int spconv_split_pack(const float* weight, int cin, int cout, int kk, int transpose, int flip, void* w_packed,
+                      hipStream_t st);
+int spconv_split_fwd_io(const void* x, const int32_t* nbr, int64_t m_out, const void* wp, const float* bias,
+                        const void* addend, const int32_t* row_order, int cin, int cout, void* y, int relu, int io,
+                        hipStream_t st, const float* x_add);
+int spconv_split_fwd(const float* x, const int32_t* nbr, int64_t m_out, const void* wp, const float* bias,
+                     const float* addend, const int32_t* row_order, int cin, int cout, float* y, int relu, hipStream_t st);
+// linear_stream.hip: the row-streaming schedule of the dense Linear layers with cin <= 192 (1 = not its shape)
+int linear_stream_fwd(const float* x, int64_t m, const void* wp, const float* bias, const float* addend, int cin, int cout,
+                      float* y, int io, hipStream_t st);
+// wgrad_split.hip: sparse-conv weight gradient.  dw == nullptr: the partial blocks only, *chunks_out = their count
+size_t wgrad_split_sparse_workspace_bytes(int64_t m_out, int cin, int cout);
+int wgrad_split_sparse(const void* x, const float* dy, const int32_t* nbr, int64_t m_out, int cin, int cout, float* dw,
+                       void* workspace, size_t workspace_bytes, hipStream_t st, int32_t* chunks_out, bool x_bf16);
+// wgrad_dense.hip: the fixed-order sum of `chunks` partial blocks
+int wgrad_chunk_reduce(const float* part, int chunks, int64_t n, int64_t nw, float* dw, float* db, hipStream_t st);
+// wgrad_dense_lds.hip: the LDS-shared form for cout % 96 == 0, cin % 48 == 0 (plan returns 1 when it takes the shape)
+int wgrad_dense_lds_plan(int64_t m, int cin, int cout, int* chunks, int64_t* rows);
+int wgrad_dense_lds_launch(const float* x, const float* dy, int64_t m, int cin, int cout, int chunks, int64_t rows, float* part,
+                           int want_bias, hipStream_t st);

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void criterion_rows_kernel(Heads hd, int 
         }
     }
     if (terms & SEG3D_CRITERION_CE) {
-        crit::block_sum2(loss, cnt);
+        block_sum<kThreads>(loss, cnt);
         if (threadIdx.x == 0) {
             ce_part[2 * blockIdx.x] = loss;
             ce_part[2 * blockIdx.x + 1] = cnt;

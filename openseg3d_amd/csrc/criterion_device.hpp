@@ -1,8 +1,9 @@
 // Device code of the training criterion shared by its three translation units: the per-term entries (loss.hip: 'ce' /
 // 'ohem_ce', lovasz.hip: 'lovasz') and the fused entry over all heads and both terms (criterion.hip).  Every quantity has
-// ONE expression here, so that with -ffp-contract=off the fused entry returns the bits of the per-term ones.
+// ONE expression here, so that with -ffp-contract=off the fused entry returns the bits of the per-term ones.  The sums over
+// a workgroup are wave_ops.hpp's (block_sum: wave xor tree, then the waves in ascending order), as in the other loss files.
 #pragma once
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace crit {
 
@@ -32,29 +33,6 @@ __device__ __forceinline__ bool ce_row(const float* __restrict__ row, int c, int
     return counted;
 }
 
-// sums of (a, b) over a workgroup of kThreads, in thread 0 only; fixed order: xor tree per wave, then the waves in turn
-__device__ __forceinline__ void block_sum2(float& a, float& b) {
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, SEG3D_WAVE);
-        b += __shfl_xor(b, off, SEG3D_WAVE);
-    }
-    __shared__ float red[2][kThreads / 64];
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = a;
-        red[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float sa = 0.f, sb = 0.f;
-        for (int w = 0; w < kThreads / 64; ++w) {
-            sa += red[0][w];
-            sb += red[1][w];
-        }
-        a = sa;
-        b = sb;
-    }
-}
-
 // mean over the counted rows from the row pass's per-workgroup partials part[nblocks][2]; valid in thread 0
 __device__ __forceinline__ void ce_mean(const float* __restrict__ part, int nblocks, float* mean_out, float* count_out) {
     float a = 0.f, b = 0.f;
@@ -62,7 +40,7 @@ __device__ __forceinline__ void ce_mean(const float* __restrict__ part, int nblo
         a += part[2 * i];
         b += part[2 * i + 1];
     }
-    block_sum2(a, b);
+    block_sum<kThreads>(a, b);  // valid in thread 0
     *mean_out = b > 0.f ? a / b : 0.f;
     *count_out = b;
 }
@@ -106,11 +84,7 @@ __device__ __forceinline__ int lovasz_segment_offsets(const int* __restrict__ ch
     for (int t0 = 0; t0 < nchunks; t0 += 64) {
         const int i = t0 + lane;
         const int v = i < nchunks ? chunk_cnt[i] : 0;
-        int inc = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off, SEG3D_WAVE);
-            if (lane >= off) inc += o;
-        }
+        const int inc = wave_scan_inclusive(v, lane);
         if (i < nchunks) chunk_off[i] = carry + inc - v;
         carry += __shfl(inc, 63, SEG3D_WAVE);
     }

@@ -19,7 +19,6 @@
 //            rows, wave64 shuffles -> LDS -> one record per workgroup; a fold decides kept / height
 // Counts are integers, minima are exact and the sums have one order: the result is a pure function of the inputs.  The
 // host twin below shares every recipe (the key, the bisection, the distance tests) and gives the same bits.
-#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -28,14 +27,13 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.hpp"
+#include "instance_geom.hpp"
 
 // fixed sequences of IEEE products and sums, as numpy rounds them; no fused multiply-add (see augment.hip)
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / SEG3D_WAVE;
 constexpr int kMaxDim = 16;
 constexpr int kMaxTargets = 8;
@@ -65,10 +63,6 @@ struct GroundRec {
     int32_t row;
     int32_t pad;
 };
-
-__host__ __device__ __forceinline__ int64_t label_at(const void* labels, int label_bytes, int64_t i) {
-    return label_bytes == 1 ? (int64_t) static_cast<const uint8_t*>(labels)[i] : static_cast<const int64_t*>(labels)[i];
-}
 
 // Cell of a coordinate, shifted to [0, 2^29).  Two rows within eps of each other must land in the same or in adjacent
 // cells although v / side is rounded: with side = eps * (1 + 2^-20) their exact quotients differ by less than
@@ -121,15 +115,7 @@ __host__ __device__ __forceinline__ void for_each_neighbour(const uint64_t* __re
     }
 }
 
-__host__ __device__ __forceinline__ bool closer(double d, int32_t row, double bd, int32_t brow) {
-    return d < bd || (d == bd && row < brow);
-}
-
-// np.linalg.norm over three columns (:29-31, :69): ((dx*dx + dy*dy) + dz*dz), IEEE sqrt
-__host__ __device__ __forceinline__ double dist3(double x, double y, double z, const double* c) {
-    const double dx = x - c[0], dy = y - c[1], dz = z - c[2];
-    return sqrt((dx * dx + dy * dy) + dz * dz);
-}
+// label_at, closer and dist3 (np.linalg.norm, :29-31, :69) are instance_geom.hpp's, shared with augment_instance.hip
 
 // ------------------------------------------------------------------------------------------ device
 // the running counters are the caller's counts[4], zeroed by a memset in front of the chain
@@ -270,33 +256,7 @@ __global__ __launch_bounds__(kThreads) void ext_emit_kernel(const uint64_t* __re
     if (flags[q] && c <= cap) cbegin[c] = (int32_t)q;  // cbegin has cap + 1 entries
 }
 
-// The fixed summation order of the mean (augment_instance.hip: block_sum3): thread t adds rows t, t + 256, ... in
-// ascending order, then the 256 partial sums are folded by halving.  sum3_host below does the same.
-__device__ void block_sum3(double* v, double* lds) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    for (int c = 0; c < 3; ++c) lds[c * kThreads + t] = v[c];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s)
-            for (int c = 0; c < 3; ++c) lds[c * kThreads + t] += lds[c * kThreads + t + s];
-        __syncthreads();
-    }
-    for (int c = 0; c < 3; ++c) v[c] = lds[c * kThreads];
-}
-
-__device__ double block_max(double v, double* lds) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    lds[t] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (t < s && lds[t + s] > lds[t]) lds[t] = lds[t + s];
-        __syncthreads();
-    }
-    return lds[0];
-}
-
+// centre and radius of every cluster, the mean in the one order of block_sum3 (instance_geom.hpp)
 template <typename T>
 __global__ __launch_bounds__(kThreads) void ext_stats_kernel(const T* __restrict__ pts, int dim, ExtractParams P,
                                                              const uint64_t* __restrict__ rkeys,
@@ -541,14 +501,6 @@ int ext_launch(const T* pts, int64_t n, int dim, const void* labels, int label_b
 }
 
 // ------------------------------------------------------------------------------------------ host twin
-void sum3_host(const std::vector<double>& part, double* v) {  // part [3][kThreads]: block_sum3's fold
-    std::vector<double> l(part);
-    for (int s = kThreads / 2; s > 0; s >>= 1)
-        for (int t = 0; t < s; ++t)
-            for (int c = 0; c < 3; ++c) l[c * kThreads + t] += l[c * kThreads + t + s];
-    for (int c = 0; c < 3; ++c) v[c] = l[c * kThreads];
-}
-
 int32_t find_host(std::vector<int32_t>& parent, int32_t x) {
     while (parent[x] != x) x = parent[x];
     return x;

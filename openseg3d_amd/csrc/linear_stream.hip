@@ -19,7 +19,6 @@
 // prefetch is pinned in place, and the four waves of a workgroup keep the SAME rows in flight.)
 // Products, their order and the accumulator's start (the bias) are those of the old kernel: results are bit-identical.
 #include <atomic>
-#include <cstdlib>
 
 #include "split_bf16.hpp"
 
@@ -157,10 +156,7 @@ int launch_stream_nb(const float* x, int64_t m, const void* wp, const float* bia
 // The premise was wrong: ALONE the old kernel moves 192 -> 192 at 4.5 TB/s (its 34.7 us in the step's profile is what sharing
 // the chip with the weight-gradient stream costs), and this schedule's 147 KB W prologue per workgroup (256 workgroups pulling
 // 38 MB through L2 before the first row is read) costs what the rolling prefetch saves.  Kept as a parity-tested experiment.
-static const bool g_linear_stream = [] {
-    const char* e = getenv("SEG3D_LINEAR_STREAM");
-    return e && atoi(e) == 1;
-}();
+static const bool g_linear_stream = env_int("SEG3D_LINEAR_STREAM", 0) == 1;
 
 // seg3d_debug_set_linear_stream (parity tests pin the opt-in schedule with it): 1 = on, 0 = off, -1 = the environment's choice
 static std::atomic<int> g_linear_stream_forced{-1};

@@ -19,7 +19,6 @@
 // each 16-byte load instruction reads whole sectors; W is packed in the same channel order), the next step's requested before this step's 96 MFMAs.  Column groups of one row block are neighbours on one XCD
 // (they re-read the same rows from its L2).  Optional epilogue: y * scale + shift per column and ReLU (the eval form of the
 // BatchNorm1d + ReLU that follows every one of these layers; two roundings, exactly the separate pass's arithmetic).
-#include <cstdlib>
 #include <type_traits>
 
 #include "split_bf16.hpp"
@@ -238,16 +237,8 @@ __global__ __launch_bounds__(kThreads, WPS) void linear_x6_kernel(const float* _
 }
 
 // SEG3D_X6_RT (A/B): 16-row tiles per wave, 4 or 2 (default 2); SEG3D_X6_WPS: resident workgroups per CU of the 2-tile form, 3 or 4
-static const int g_x6_rt = [] {
-    const char* e = getenv("SEG3D_X6_RT");
-    const int v = e ? atoi(e) : 2;
-    return v == 4 ? 4 : 2;
-}();
-static const int g_x6_wps = [] {
-    const char* e = getenv("SEG3D_X6_WPS");
-    const int v = e ? atoi(e) : 3;
-    return v == 4 ? 4 : 3;
-}();
+static const int g_x6_rt = env_int("SEG3D_X6_RT", 2) == 4 ? 4 : 2;
+static const int g_x6_wps = env_int("SEG3D_X6_WPS", 3) == 4 ? 4 : 3;
 
 }  // namespace
 

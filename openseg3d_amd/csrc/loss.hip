@@ -31,7 +31,7 @@ __global__ __launch_bounds__(kThreads) void ce_fwd_kernel(const float* __restric
             cnt += 1.f;
         }
     }
-    crit::block_sum2(loss, cnt);
+    block_sum<kThreads>(loss, cnt);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = loss;
         part[2 * blockIdx.x + 1] = cnt;

@@ -21,36 +21,13 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocks = 1024;
 constexpr int kDiceRows = 128;  // rows (= threads) of a dice workgroup: 128 * 65 floats of LDS at C = 64
-
-// sum of a and b over the workgroup, valid in thread 0
-template <int THREADS>
-__device__ __forceinline__ void block_sum2(double& a, double& b) {
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, SEG3D_WAVE);
-        b += __shfl_xor(b, off, SEG3D_WAVE);
-    }
-    __shared__ double red[2][THREADS / 64];
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = a;
-        red[1][threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = 0.0;
-        b = 0.0;
-        for (int w = 0; w < THREADS / 64; ++w) {
-            a += red[0][w];
-            b += red[1][w];
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------- focal
 enum { kGammaZero = 0, kGammaOne = 1, kGammaTwo = 2, kGammaAny = 3 };
@@ -105,7 +82,7 @@ __global__ __launch_bounds__(kThreads) void focal_fwd_kernel(const float* __rest
         if (j == 0) cnt += 1.f;
     }
     double a = loss, b = cnt;
-    block_sum2<kThreads>(a, b);
+    block_sum<kThreads>(a, b);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = a;
         part[2 * blockIdx.x + 1] = b;
@@ -120,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void focal_finalize_kernel(const double* 
         a += part[2 * i];
         b += part[2 * i + 1];
     }
-    block_sum2<kThreads>(a, b);
+    block_sum<kThreads>(a, b);
     if (threadIdx.x == 0) {
         stats[0] = (float)(mean ? (b > 0.0 ? a / (b * c) : 0.0) : a);
         stats[1] = (float)b;
@@ -228,7 +205,7 @@ __global__ __launch_bounds__(kDiceRows) void dice_fwd_kernel(const float* __rest
         __syncthreads();
     }
     double s = acc, unused = 0.0;
-    block_sum2<kDiceRows>(s, unused);
+    block_sum<kDiceRows>(s, unused);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -236,7 +213,7 @@ __global__ __launch_bounds__(kThreads) void dice_finalize_kernel(const double* _
                                                                  float* __restrict__ out) {
     double a = 0.0, unused = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += kThreads) a += part[i];
-    block_sum2<kThreads>(a, unused);
+    block_sum<kThreads>(a, unused);
     if (threadIdx.x == 0) out[0] = (float)(a * scale);
 }
 

@@ -77,27 +77,6 @@ __device__ __forceinline__ void hist_flush(const uint32_t* lds_hist, uint32_t* _
     }
 }
 
-// inclusive prefix sum of v over the workgroup's threads, and the total
-__device__ __forceinline__ uint32_t block_scan_inclusive(uint32_t v, uint32_t* total) {
-    __shared__ uint32_t wsum[kThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, SEG3D_WAVE);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();  // wsum may still be read from an earlier call
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < kThreads / 64; ++w) {
-        if (w < wave) inc += wsum[w];
-        t += wsum[w];
-    }
-    *total = t;
-    return inc;
-}
-
 // The step between two passes, by a whole workgroup: from the histogram of digit D over the rows that match the digits
 // before it, and the number `remain` still to pick among them, the digit's value d with
 //   count(digit > d) < remain <= count(digit >= d)
@@ -115,7 +94,7 @@ __device__ __forceinline__ SelectState select_digit(const uint32_t* __restrict__
         own += bins[j];
     }
     uint32_t total;
-    const uint32_t inc = block_scan_inclusive(own, &total);
+    const uint32_t inc = block_scan_inclusive<kThreads>(own, &total);
     const uint32_t above = total - inc;  // rows in the bins of the threads above this one
     SelectState prev;
     if constexpr (D == 0) {
@@ -194,24 +173,10 @@ __global__ __launch_bounds__(kThreads) void row_pass_kernel(const float* __restr
     if (RATIO) {
         hist_flush(lds_hist, hist);
     } else {
-        for (int off = 32; off > 0; off >>= 1) {
-            loss += __shfl_xor(loss, off, SEG3D_WAVE);
-            den += __shfl_xor(den, off, SEG3D_WAVE);
-        }
-        __shared__ double red[2][kThreads / 64];
-        if ((threadIdx.x & 63) == 0) {
-            red[0][threadIdx.x >> 6] = loss;
-            red[1][threadIdx.x >> 6] = den;
-        }
-        __syncthreads();
+        block_sum<kThreads>(loss, den);
         if (threadIdx.x == 0) {
-            double a = 0.0, b = 0.0;
-            for (int w = 0; w < kThreads / 64; ++w) {
-                a += red[0][w];
-                b += red[1][w];
-            }
-            part[2 * blockIdx.x] = a;
-            part[2 * blockIdx.x + 1] = b;
+            part[2 * blockIdx.x] = loss;
+            part[2 * blockIdx.x + 1] = den;
         }
     }
 }
@@ -247,7 +212,7 @@ __global__ __launch_bounds__(kThreads) void tie_count_kernel(const uint32_t* __r
     uint32_t mine = 0;
     for (int64_t r = begin + threadIdx.x; r < end; r += kThreads) mine += keys[r] == st.prefix ? 1u : 0u;
     uint32_t total;
-    block_scan_inclusive(mine, &total);
+    block_scan_inclusive<kThreads>(mine, &total);
     if (threadIdx.x == 0) tie_count[blockIdx.x] = total;
 }
 
@@ -260,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void select_rows_kernel(const uint32_t* _
     uint32_t before = 0;  // ties in the workgroups in front of this one
     for (int b = threadIdx.x; b < (int)blockIdx.x; b += kThreads) before += tie_count[b];
     uint32_t ties_before;
-    block_scan_inclusive(before, &ties_before);
+    block_scan_inclusive<kThreads>(before, &ties_before);
     int64_t begin, end;
     block_rows(n, rows_per_block, &begin, &end);
     double loss = 0.0;
@@ -269,7 +234,7 @@ __global__ __launch_bounds__(kThreads) void select_rows_kernel(const uint32_t* _
         const uint32_t key = r < end ? keys[r] : 0u;
         const bool tie = key != 0u && key == T;
         uint32_t chunk_ties;
-        const uint32_t inc = block_scan_inclusive(tie ? 1u : 0u, &chunk_ties);
+        const uint32_t inc = block_scan_inclusive<kThreads>(tie ? 1u : 0u, &chunk_ties);
         const bool counted = key != 0u && (key > T || (tie && ties_before + inc - 1u < admit));
         if (r < end) {
             if (counted)
@@ -279,13 +244,8 @@ __global__ __launch_bounds__(kThreads) void select_rows_kernel(const uint32_t* _
         }
         ties_before += chunk_ties;
     }
-    for (int off = 32; off > 0; off >>= 1) loss += __shfl_xor(loss, off, SEG3D_WAVE);
-    __shared__ double red[kThreads / 64];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = loss;
-    __syncthreads();
+    const double a = block_sum<kThreads>(loss);
     if (threadIdx.x == 0) {
-        double a = 0.0;
-        for (int w = 0; w < kThreads / 64; ++w) a += red[w];
         part[2 * blockIdx.x] = a;
         part[2 * blockIdx.x + 1] = 0.0;
     }

@@ -13,18 +13,6 @@
 // Algorithmic bytes per launch: P*(Cin+Cout)*4 + 27*Cin*Cout*4 + P*8, P = active pairs.
 #include "common.hpp"
 
-size_t spconv_split_packed_bytes(int cin_op, int cout_op, int kk);
-int spconv_split_pack(const float* weight, int cin, int cout, int kk, int transpose, int flip, void* w_packed,
-                      hipStream_t st);
-int spconv_split_fwd_io(const void* x, const int32_t* nbr, int64_t m_out, const void* wp, const float* bias,
-                        const void* addend, const int32_t* row_order, int cin, int cout, void* y, int relu, int io,
-                        hipStream_t st, const float* x_add);
-int spconv_split_fwd(const float* x, const int32_t* nbr, int64_t m_out, const void* wp, const float* bias,
-                     const float* addend, const int32_t* row_order, int cin, int cout, float* y, int relu, hipStream_t st);
-size_t wgrad_split_sparse_workspace_bytes(int64_t m_out, int cin, int cout);  // wgrad_split.hip
-int wgrad_split_sparse(const void* x, const float* dy, const int32_t* nbr, int64_t m_out, int cin, int cout, float* dw,
-                       void* workspace, size_t workspace_bytes, hipStream_t st, int32_t* chunks_out, bool x_bf16);
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -14,8 +14,6 @@
 //   inline asm, so the compiler does not drain them in front of the fragment reads -- one hand-placed vmcnt(0) + barrier
 //   per chunk;  tile-level skipping of offsets no row of the tile uses, optional processing order of the rows (parity-
 //   grouped strided / inverse tables), bias / addend / ReLU epilogue exactly as spconv_split_kernel.
-#include <cstdlib>
-
 #include "split_bf16.hpp"
 
 namespace {
@@ -256,7 +254,7 @@ int seg3d_spconv_fwd_presplit(const void* xs, const int32_t* nbr, int64_t m_out,
     hipStream_t st = as_stream(stream);
     const __bf16* x2 = static_cast<const __bf16*>(xs);
     // 192-column tiles while the launch has >= 400 row tiles, 96-column tiles on the small deep levels (more workgroups)
-    static const int nbt_env = getenv("SEG3D_CONV_DMA_NBT") ? atoi(getenv("SEG3D_CONV_DMA_NBT")) : 0;
+    static const int nbt_env = env_int("SEG3D_CONV_DMA_NBT", 0);
     const int nb = cout / 16;
     int pick = (nb % 12 == 0 && ceil_div64(m_out, 128) >= 400) ? 12 : 6;
     if (nbt_env == 6 || (nbt_env == 12 && nb % 12 == 0)) pick = nbt_env;

@@ -21,7 +21,6 @@
 // in flight while chunk c computes (their waits sit behind the MFMAs); one barrier per chunk.  Offsets with no active
 // neighbour in the whole tile are never visited; a wave whose own rows have none skips the MFMAs.
 #include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 #include "split_bf16.hpp"
@@ -516,10 +515,7 @@ __global__ __launch_bounds__(256, 2) void spconv_split_kernel(const void* __rest
 // bound by the rate of gather requests, not by one wave's round trip.
 constexpr int kDeepMaxNbt = 6;
 static bool conv_depth2() {
-    static const bool on = [] {
-        const char* e = getenv("SEG3D_CONV_DEPTH");
-        return e && atoi(e) == 2;
-    }();
+    static const bool on = env_int("SEG3D_CONV_DEPTH", 0) == 2;
     return on;
 }
 
@@ -529,19 +525,13 @@ int launch_split(const void* x, const int32_t* nbr, int64_t m_out, const void* w
                  const float* x_add = nullptr, LnEpilogue ln = LnEpilogue{nullptr, nullptr, 0.f}) {
     dim3 grid((unsigned)ceil_div64(m_out, 4 * RB * 16), (unsigned)((cout / 16) / NBT));
     // SEG3D_CONV_XCD_RUN (A/B, sparse tables only): every XCD walks one contiguous run of row tiles
-    static const int xcd_run = [] {
-        const char* e = getenv("SEG3D_CONV_XCD_RUN");
-        return (e && atoi(e) == 1) ? 1 : 0;
-    }();
+    static const int xcd_run = env_int("SEG3D_CONV_XCD_RUN", 0) == 1 ? 1 : 0;
     if (xcd_run && nbr != nullptr && io == 0 && grid.x >= 64) {
         grid.x = (grid.x + 7) / 8 * 8;
         relu |= 2;
     }
     // SEG3D_LINEAR_COLGROUPS (A/B): 0 = the column groups of a dense Linear layer as the grid's y dimension (round 4)
-    static const int col_adjacent = [] {
-        const char* e = getenv("SEG3D_LINEAR_COLGROUPS");
-        return (e && atoi(e) == 0) ? 0 : 1;
-    }();
+    static const int col_adjacent = env_int("SEG3D_LINEAR_COLGROUPS", 1) == 0 ? 0 : 1;
     if (col_adjacent && nbr == nullptr && grid.y > 1 && (io == 0 || io == 3 || io == 4)) {
         grid.x = (grid.x + 7) / 8 * 8 * grid.y;
         grid.y = 1;
@@ -603,20 +593,13 @@ int spconv_split_pack(const float* weight, int cin, int cout, int kk, int transp
 
 // Forced column-block width (x16) of the gather-GEMM: SEG3D_CONV_NBT read ONCE at load time, or set by
 // seg3d_debug_set_conv_nbt (parity tests pin each instantiation with it); 0 = automatic.
-static std::atomic<int> g_forced_nbt{[] {
-    const char* e = getenv("SEG3D_CONV_NBT");
-    return e ? atoi(e) : 0;
-}()};
+static std::atomic<int> g_forced_nbt{env_int("SEG3D_CONV_NBT", 0)};
 
 extern "C" int seg3d_debug_set_conv_nbt(int32_t nbt) {
     if (nbt != 0 && nbt != 1 && nbt != 2 && nbt != 3 && nbt != 4 && nbt != 6 && nbt != 8 && nbt != 12) return SEG3D_EINVAL;
     g_forced_nbt.store(nbt, std::memory_order_relaxed);
     return SEG3D_OK;
 }
-
-// linear_stream.hip: the row-streaming schedule of the dense Linear layers with cin <= 192 (1 = not its shape)
-int linear_stream_fwd(const float* x, int64_t m, const void* wp, const float* bias, const float* addend, int cin, int cout,
-                      float* y, int io, hipStream_t st);
 
 static int split_fwd_impl(const void* x, const int32_t* nbr, int64_t m_out, const void* wp, const float* bias,
                           const void* addend, const int32_t* row_order, int cin, int cout, void* y, int relu, int io,

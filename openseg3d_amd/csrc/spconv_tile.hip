@@ -25,7 +25,6 @@
 // "direct": the image is refilled per offset with that offset's 128 neighbour rows.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "split_bf16.hpp"
@@ -557,20 +556,13 @@ __global__ __launch_bounds__(kThreads, 2) void spconv_tile_kernel(const void* __
 // only by a -DSEG3D_TILE_DBG build (tools/r4_tile_dbg.sh); the shipped library ignores the variable and its kernels carry
 // no trace of the experiments (TILE_DBG(x) is the constant 0).
 #ifdef SEG3D_TILE_DBG
-static const int g_tile_dbg = [] {
-    const char* e = getenv("SEG3D_TILE_DBG");
-    return e ? atoi(e) : 0;
-}();
+static const int g_tile_dbg = env_int("SEG3D_TILE_DBG", 0);
 #else
 static const int g_tile_dbg = 0;
 #endif
 
 // SEG3D_TILE_RUN (A/B): consecutive tiles per XCD run (0 or anything outside 1..64 = automatic)
-static const int g_tile_run = [] {
-    const char* e = getenv("SEG3D_TILE_RUN");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 1 && v <= 64) ? v : 0;
-}();
+static const int g_tile_run = env_int_in("SEG3D_TILE_RUN", 1, 64, 0);
 
 template <int WR, int WC, int NBW, bool KS = false>
 int launch_tile(const void* x, const int32_t* nbr, const PlanView& pv, int64_t m_out, const void* wp, const float* bias,
@@ -616,11 +608,7 @@ static int tile_layout(int cin, int cout) {
 }
 
 // SEG3D_TILE_LAYOUT (A/B): force a layout id where it divides cout
-static const int g_tile_layout = [] {
-    const char* e = getenv("SEG3D_TILE_LAYOUT");
-    const int v = e ? atoi(e) : 0;
-    return (v >= 1 && v <= 5) ? v : 0;  // anything else: automatic
-}();
+static const int g_tile_layout = env_int_in("SEG3D_TILE_LAYOUT", 1, 5, 0);  // anything else: automatic
 
 int spconv_tile_fwd(const void* x, const int32_t* nbr, const void* plan, int64_t m_out, const void* wp, const float* bias,
                     const void* addend, int cin, int cout, void* y, int relu, int io, hipStream_t st) {

@@ -18,15 +18,9 @@
 // Block order: id -> (xcd = id % 8, k = id / 8), chunk = 8 * (k / tiles) + xcd, block = k % tiles, so the
 // workgroups that read the same rows (all blocks of a chunk) are dispatched back to back on the same XCD
 // and share its L2.
-#include <cstdlib>
 #include <type_traits>
 
 #include "split_bf16.hpp"
-
-// wgrad_dense_lds.hip: the LDS-shared form for cout % 96 == 0, cin % 48 == 0 (1 = it takes the shape)
-int wgrad_dense_lds_plan(int64_t m, int cin, int cout, int* chunks, int64_t* rows);
-int wgrad_dense_lds_launch(const float* x, const float* dy, int64_t m, int cin, int cout, int chunks, int64_t rows, float* part,
-                           int want_bias, hipStream_t st);
 
 namespace {
 
@@ -48,10 +42,7 @@ struct Plan {
 // level gains (384 -> 768 70.4 -> 63.7, 384 -> 384 39.6 -> 35.9); training step 42.3 -> 42.7 ms.  The waves of a group drift
 // apart by more rows than the 32 KB L1 holds, so the shared slab is fetched from L2 by each of them anyway, and a wave's chain
 // is four times as long.
-static const bool g_wgrad_group = [] {
-    const char* e = getenv("SEG3D_WGRAD_GROUP");
-    return e && atoi(e) == 1;
-}();
+static const bool g_wgrad_group = env_int("SEG3D_WGRAD_GROUP", 0) == 1;
 
 Plan plan(int64_t m, int cin, int cout, bool allow_lds = false) {
     Plan p{(cout + 63) / 64, (cin + 63) / 64, 0, 32, 0, 0};
@@ -94,8 +85,7 @@ Plan plan(int64_t m, int cin, int cout, bool allow_lds = false) {
     // 2 waves per SIMD = 2 workgroups per CU = 512 resident workgroups.  Few blocks per chunk: one resident
     // round of long chunks (per-workgroup prologue / reduction overhead matters); many blocks per chunk: two
     // rounds.  Chunks map to XCDs round-robin, so their number is kept a multiple of 8.
-    int target = tiles >= 16 ? 1024 : 512;
-    if (const char* e = getenv("SEG3D_WGRAD_TARGET")) target = atoi(e);
+    const int target = env_int("SEG3D_WGRAD_TARGET", tiles >= 16 ? 1024 : 512);  // (read on every call)
     int64_t chunks = target / tiles / 8 * 8;
     if (chunks < 8) chunks = 8;
     int64_t rows = (m + chunks - 1) / chunks;
@@ -470,10 +460,7 @@ static void launch_dense(const Plan& p, const void* x, bool x_bf16, const float*
     // @58 k 27.2 -> 37.1 us, 384 -> 768 @19 k 69.4 -> 91.7); with 256 / 512 workgroups 4.95 / 4.79 ms.  A second set at two
     // waves per SIMD does not fit (101 - 223 spilled registers).  The kernel needs its second wave per SIMD (the other wave's
     // conversions under this wave's MFMAs) more than it needs bytes in flight.
-    static const int depth = [] {
-        const char* e = getenv("SEG3D_WGRAD_DENSE_DEPTH");
-        return (e && atoi(e) == 3) ? 3 : 1;
-    }();
+    static const int depth = env_int("SEG3D_WGRAD_DENSE_DEPTH", 1) == 3 ? 3 : 1;
     if (!x_bf16 && depth == 3) {
         hipLaunchKernelGGL((wgrad_dense_kernel<false, false, 3>), dim3(blocks), dim3(kThreads), 0, st, x, dy, m, cin, cout, (int)p.rows,
                            p.nbi, tiles, part, want_bias, 0, nullptr, nullptr);

@@ -17,14 +17,9 @@
 // as before: no atomics, bit-reproducible run to run.  db rides in the matrix pipe: a fragment of ones against the dy
 // fragments (hi and lo: the column sum of the split operand, 2^-17 relative per element), in the waves of the first ci block.
 #include <atomic>
-#include <cstdlib>
 #include <type_traits>
 
 #include "split_bf16.hpp"
-
-int wgrad_dense_lds_plan(int64_t m, int cin, int cout, int* chunks, int64_t* rows);
-int wgrad_dense_lds_launch(const float* x, const float* dy, int64_t m, int cin, int cout, int chunks, int64_t rows, float* part,
-                           int want_bias, hipStream_t st);
 
 namespace {
 
@@ -161,15 +156,8 @@ __global__ __launch_bounds__(64 * WA * WB, 2) void wgrad_dense_lds_kernel(const 
 // Half the L2 -> L1 row traffic and a third of the split instructions bought nothing: the direct-to-fragment kernel is not
 // bound by either (DESIGN.md section 6 had said the stream was the bound), and the four times larger partial blocks (34 - 36 MB
 // per launch against 8 - 17) cost what the reduce then pays.  Kept as a parity-tested experiment.
-static const int g_lds_on = [] {
-    const char* e = getenv("SEG3D_WGRAD_LDS");
-    return (e && atoi(e) == 1) ? 1 : 0;
-}();
-static const int g_lds_target = [] {
-    const char* e = getenv("SEG3D_WGRAD_LDS_TARGET");
-    const int v = e ? atoi(e) : 512;
-    return (v >= 64 && v <= 4096) ? v : 512;
-}();
+static const int g_lds_on = env_int("SEG3D_WGRAD_LDS", 0) == 1 ? 1 : 0;
+static const int g_lds_target = env_int_in("SEG3D_WGRAD_LDS_TARGET", 64, 4096, 512);
 
 // seg3d_debug_set_wgrad_lds (parity tests pin the opt-in kernel with it): 1 = on, 0 = off, -1 = the environment's choice
 static std::atomic<int> g_lds_forced{-1};

@@ -18,11 +18,9 @@
 // order -- bit-reproducible, no memset of dw.
 // Block order: id -> (xcd = id % 8, j = id / 8), unit = 8 * (j / tiles) + xcd = (chunk, offset), block = j % tiles:
 // the workgroups that read the same gathered rows are dispatched back to back on one XCD and share its L2.
-#include <cstdlib>
+#include <limits.h>
 
 #include "split_bf16.hpp"
-
-int wgrad_chunk_reduce(const float* part, int chunks, int64_t n, int64_t nw, float* dw, float* db, hipStream_t st);
 
 #ifdef SEG3D_WGRAD_STAMP
 // In-kernel phase clocks of the wide kernel (tools/probes/wgrad_stamps.py; -DSEG3D_WGRAD_STAMP build only, never shipped):
@@ -85,11 +83,8 @@ Plan plan(int64_t m, int cin, int cout) {
     const int tiles = p.nbo * p.nbi;
     // a wave should see >= ~8 steps (about a third of the rows of an offset are valid pairs): chunks of ~3000
     // rows; at least ~1000 workgroups per launch
-    static const int rows_target = [] {
-        const char* e = getenv("SEG3D_WGRAD_SPARSE_ROWS");
-        const int v = e ? atoi(e) : 3072;
-        return v >= 64 ? v : 3072;  // 0 / non-numeric / tiny values: the default (never a division by zero)
-    }();
+    // 0 / non-numeric / tiny values: the default (never a division by zero)
+    static const int rows_target = env_int_in("SEG3D_WGRAD_SPARSE_ROWS", 64, INT_MAX, 3072);
     int64_t chunks = m / rows_target;
     const int64_t need = (1024 + 27 * tiles - 1) / (27 * tiles);
     if (chunks < need) chunks = need;
@@ -567,17 +562,11 @@ int wgrad_split_sparse(const void* x, const float* dy, const int32_t* nbr, int64
     const Plan p = plan(m_out, cin, cout);
     float* part = static_cast<float*>(workspace);
     const int units = p.chunks * 27;
-    static const bool narrow_only = getenv("SEG3D_WGRAD_NARROW") != nullptr;  // A/B switch for profiling
+    static const bool narrow_only = env_set("SEG3D_WGRAD_NARROW");  // A/B switch for profiling
     // SEG3D_WGRAD_CENTER_FIRST (A/B): 0 = units in (chunk, offset) order (round 4)
-    static const int center_first = [] {
-        const char* e = getenv("SEG3D_WGRAD_CENTER_FIRST");
-        const int cf = (e && atoi(e) == 0) ? 0 : 1;
-        // SEG3D_WGRAD_XCD_BLOCK (A/B): consecutive units per XCD (1 = round-robin, round 4's order)
-        const char* b = getenv("SEG3D_WGRAD_XCD_BLOCK");
-        int xb = b ? atoi(b) : 1;
-        if (xb < 1 || xb > 64) xb = 1;
-        return cf | (xb << 8);
-    }();
+    // SEG3D_WGRAD_XCD_BLOCK (A/B): consecutive units per XCD (1 = round-robin, round 4's order), in bits 8 and up
+    static const int center_first = (env_int("SEG3D_WGRAD_CENTER_FIRST", 1) == 0 ? 0 : 1) |
+                                    (env_int_in("SEG3D_WGRAD_XCD_BLOCK", 1, 64, 1) << 8);
     const int xcd_block = center_first >> 8;
     const int unit_slots = (units + 8 * xcd_block - 1) / (8 * xcd_block) * (8 * xcd_block);  // grid padding: whole blocks on every XCD
     // 128-wide blocks only where they add no padding (C = 256, 384, 768; not 192 = 1.5 blocks)
@@ -587,21 +576,14 @@ int wgrad_split_sparse(const void* x, const float* dy, const int32_t* nbr, int64
     // MFMAs (384 -> 192 inverse 274 -> 196 us, 192 -> 96 inverse 190 -> 151 us, 384 -> 192 submanifold 766 -> 719 us); square
     // 192 x 192 (78 % padding on MFMA-heavy submanifold tables) loses: 395 -> 492 us.  SEG3D_WGRAD_WIDE_MIN=n (A/B) pads every
     // layer with both widths >= n.
-    static const int wide_min = [] {
-        const char* e = getenv("SEG3D_WGRAD_WIDE_MIN");
-        return e ? atoi(e) : 0;
-    }();
+    static const int wide_min = env_int("SEG3D_WGRAD_WIDE_MIN", 0);
     const int cmin = cin < cout ? cin : cout, cmax = cin < cout ? cout : cin;
     const bool wide_padded = (wide_min > 0 && cmin >= wide_min) || (cin != cout && cmin >= 96 && cmax >= 192);
     if ((fits128 || wide_padded) && !narrow_only) {
         const int nbo = (cout + 127) / 128, nbi = (cin + 127) / 128, tiles = nbo * nbi;
         const unsigned blocks = (unsigned)unit_slots * (unsigned)tiles;
         // SEG3D_WGRAD_DEPTH (A/B): gather steps in flight per wave (1 or 2)
-        static const int depth = [] {
-            const char* e = getenv("SEG3D_WGRAD_DEPTH");
-            const int v = e ? atoi(e) : 1;
-            return v == 2 ? 2 : 1;
-        }();
+        static const int depth = env_int("SEG3D_WGRAD_DEPTH", 1) == 2 ? 2 : 1;
 #define SEG3D_LAUNCH_WIDE(XB_, D_)                                                                                             \
     hipLaunchKernelGGL((wgrad_sparse_wide_kernel<XB_, D_>), dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout, \
                        (int)p.rows, nbi, tiles, units, part, center_first)
@@ -609,10 +591,7 @@ int wgrad_split_sparse(const void* x, const float* dy, const int32_t* nbr, int64
         // buffer (37 KB of LDS, 162 VGPRs) and THREE workgroups per CU -- the kernel waits for gathered rows 44 % of the time, and
         // half more resident waves hide more of it than the second barrier per step costs: the 11 wide layers of the headline
         // step 4.95 -> 4.76 ms alone (inverse tables -11 %, 768 -> 384 -6 %), training step 42.95 -> 42.77 ms, same bits.
-        static const bool single = [] {
-            const char* e = getenv("SEG3D_WGRAD_SB");
-            return !(e && atoi(e) == 0);
-        }();
+        static const bool single = env_int("SEG3D_WGRAD_SB", 1) != 0;
 #define SEG3D_LAUNCH_WIDE_SB(XB_)                                                                                                   \
     hipLaunchKernelGGL((wgrad_sparse_wide_kernel<XB_, 1, true>), dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout, \
                        (int)p.rows, nbi, tiles, units, part, center_first)

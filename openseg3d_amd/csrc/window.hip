@@ -14,9 +14,6 @@
 // replaces the atomic-order rank of the reference's CUDA op.
 #include "common.hpp"
 
-int group_index_launch(const int32_t* gid, int64_t n, int64_t ng, int32_t* rank, int32_t* order, int32_t* offsets,
-                       void* workspace, hipStream_t st, uint32_t** count_out, uint32_t** offs_out);
-
 namespace {
 
 constexpr int kThreads = 256;
