@@ -473,6 +473,43 @@ int seg3d_window_attn_bwd(const float* q, const float* k, const float* v, int32_
                           int32_t lddv, float* dtau, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* The two constructor options of the reference's attention layer the entries above do not take --
+ *      seg3d/models/layers/cosine_msa.py:413-432 (non_shared_tau), :156-160 (tau [1, H, 1, 1] clamped per head),
+ *      :163-165 (cosine=False: scores q.k / sqrt(dh), no normalisation, no tau),
+ *      point_transformer_layer.py:222-231 (WindowAttention(..., cosine, tau_min)).
+ * mode SEG3D_ATTN_COSINE: n_tau = 1 (the shared tau: the kernels and the bits of seg3d_window_attn_fwd / _bwd) or
+ *   n_tau = heads: head h uses max(tau[h], tau_min).  The forward takes the fixed or the running softmax maximum head by
+ *   head; the backward stores dtau[h] for every head (per-wave / per-tile partials of ONE head each in the workspace, summed
+ *   in a fixed order, no atomics: identical from run to run), exactly 0 while tau[h] <= tau_min.
+ * mode SEG3D_ATTN_DOT: n_tau = 0, tau = NULL, dtau = NULL, tau_min is ignored.  out_i = softmax_j(<q_i, k_j> / sqrt(dh)) . v_j;
+ *   scores are unbounded, so every query row keeps a running maximum and lse is the true log-sum-exp; the backward goes
+ *   straight to q and k.
+ * Everything else -- operands, window index, dropout, head geometries (seg3d_window_attn_supported), schedule
+ * (seg3d_window_attn_schedule) -- is as above, except that per-head tau at dh 6 runs the vector-ALU forward (exact fp32
+ * scores) whenever an lse is given, with or without dropout; the ignored win_tile0 is gone.  SEG3D_EINVAL: a mode other than the two,
+ * n_tau that is neither 1 nor heads (cosine) or not 0 (dot), tau given in dot mode or missing in cosine mode, a dtau that does
+ * not match the mode (missing in cosine, given in dot), rows that are not 16-byte aligned, a refused head geometry.
+ * SEG3D_EWORKSPACE: the backward's workspace is smaller than seg3d_window_attn_workspace_bytes_modes says (0 = refused
+ * arguments).  Empty inputs (m, windows, tiles or chunks = 0) return SEG3D_OK; dtau[0 .. n_tau) is zeroed when given. */
+#define SEG3D_ATTN_COSINE 0
+#define SEG3D_ATTN_DOT 1
+size_t seg3d_window_attn_workspace_bytes_modes(int64_t m, int32_t n_tiles, int32_t heads, int32_t dh, int32_t mode,
+                                               int32_t n_tau);
+int seg3d_window_attn_fwd_modes(const float* q, const float* k, const float* v, int32_t ldq, int32_t ldk, int32_t ldv,
+                                const int32_t* tok, const int32_t* win_start, const int32_t* win_count,
+                                const int32_t* tile_item, int32_t n_tiles, const int32_t* qg_item, int32_t n_qgroups,
+                                int64_t m, int32_t n_windows, int32_t heads, int32_t dh, int32_t mode, const float* tau,
+                                int32_t n_tau, float tau_min, float dropout_p, uint64_t dropout_seed, float* out, float* lse,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int seg3d_window_attn_bwd_modes(const float* q, const float* k, const float* v, int32_t ldq, int32_t ldk, int32_t ldv,
+                                const float* out, const float* dout, const float* lse, const int32_t* tok,
+                                const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item,
+                                int32_t n_tiles, const int32_t* qg_item, int32_t n_qgroups, int64_t m, int32_t n_windows,
+                                int32_t heads, int32_t dh, int32_t mode, const float* tau, int32_t n_tau, float tau_min,
+                                float dropout_p, uint64_t dropout_seed, float* dq, float* dk, float* dv, int32_t lddq,
+                                int32_t lddk, int32_t lddv, float* dtau, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * a12, a22  row-wise normalisation layers on [m, c] features (c multiple of 4).
  * LayerNorm of the post-norm encoder layer (point_transformer_layer.py:289-298), fused with the residual:

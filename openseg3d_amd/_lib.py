@@ -12,8 +12,9 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libseg3d_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
+ATTN_COSINE, ATTN_DOT = 0, 1  # SEG3D_ATTN_* of the header
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 55
+ABI_VERSION = 56
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -95,6 +96,12 @@ SIGNATURES = {
     "seg3d_window_attn_bwd": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _p,
                                              _i32, _i64, _i32, _i32, _i32, _p, _f, _f, _u64, _p, _p, _p, _i32, _i32, _i32,
                                              _p, _p, _sz, _p]),
+    "seg3d_window_attn_workspace_bytes_modes": (_sz, [_i64, _i32, _i32, _i32, _i32, _i32]),
+    "seg3d_window_attn_fwd_modes": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _p, _i32,
+                                                   _i64, _i32, _i32, _i32, _i32, _p, _i32, _f, _f, _u64, _p, _p, _p, _sz, _p]),
+    "seg3d_window_attn_bwd_modes": (ctypes.c_int, [_p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _p,
+                                                   _i32, _i64, _i32, _i32, _i32, _i32, _p, _i32, _f, _f, _u64, _p, _p, _p,
+                                                   _i32, _i32, _i32, _p, _p, _sz, _p]),
     "seg3d_layernorm_fwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _f, _i64, _i32, _p, _p, _p, _p]),
     "seg3d_layernorm_bwd_workspace_bytes": (ctypes.c_size_t, [_i64, _i32]),
     "seg3d_layernorm_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _p, _p, _p, _p, ctypes.c_size_t, _p]),

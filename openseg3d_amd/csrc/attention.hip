@@ -5,6 +5,8 @@
 //             attention_small.hip      exact-fp32 vector-ALU kernel, dh 6 with dropout (round 4: 101 / 96 -> 86 / 73 us per layer)
 //   backward  attention_fused_bwd.hip  two flash-style passes, dh 12 / 24 / 48
 //             attention_small.hip      exact-fp32 vector-ALU passes, dh 6 (windows of ~15 voxels: 360 vs 475 us per layer)
+// Every kernel above is instantiated for three attention modes (attn_common.hpp): the shared tau of seg3d_window_attn_fwd /
+// _bwd, and per-head tau and scaled dot product behind seg3d_window_attn_fwd_modes / _bwd_modes (below; cosine_msa.py:156-165).
 // Head geometries these kernels do not take (narrow heads whose count is not a multiple of 4, head widths other than the
 // four the reference builds -- pointtransformer.py:143-155: 8 heads of 6 / 12 / 24 / 48 channels) are refused with
 // SEG3D_EINVAL; seg3d_window_attn_supported says so up front.  The round-1 / round-2 fallbacks (prepare pass + core,
@@ -30,6 +32,15 @@ int bwd_path(int heads, int dh) {
 bool small_fwd_runs(int heads, int dh, float dropout_p, bool has_lse) {
     static const int small_fwd = env_int("SEG3D_ATTN_SMALL_FWD", 1);
     return (small_fwd == 2 || (small_fwd == 1 && dropout_p > 0.f)) && attn_small_supported(heads, dh) && has_lse;
+}
+
+// kernel instantiation (attn_common.hpp: kShared / kPerHead / kDot) for a mode of the header and a count of tau values;
+// -1 for a pair the entries refuse: cosine takes 1 or `heads` values, dot none
+int attn_kernel_mode(int mode, int n_tau, int heads) {
+    if (mode == SEG3D_ATTN_DOT) return n_tau == 0 ? attn::kDot : -1;
+    if (mode != SEG3D_ATTN_COSINE) return -1;
+    if (n_tau == 1) return attn::kShared;
+    return n_tau == heads && heads > 1 ? attn::kPerHead : -1;
 }
 
 bool rows_misaligned(const void* a, const void* b, const void* c, int lda, int ldb, int ldc) {
@@ -94,9 +105,9 @@ int seg3d_window_attn_fwd(const float* q, const float* k, const float* v, int32_
     if (rows_misaligned(q, k, v, ldq, ldk, ldv)) return SEG3D_EINVAL;  // rows are gathered in 16-B pieces
     if (small_fwd_runs(heads, dh, dropout_p, lse != nullptr))
         return attn_small_fwd_launch(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, tile_item, n_tiles, heads, dh, tau, tau_min,
-                                     out, lse, make_dropout(dropout_p, dropout_seed), as_stream(stream));
+                                     out, lse, make_dropout(dropout_p, dropout_seed), as_stream(stream), attn::kShared);
     return attn_fused_fwd_launch(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, tile_item, n_tiles, qg_item, n_qgroups,
-                                 heads, dh, tau, tau_min, out, lse, dropout_p, dropout_seed, as_stream(stream));
+                                 heads, dh, tau, tau_min, out, lse, dropout_p, dropout_seed, as_stream(stream), attn::kShared);
 }
 
 int seg3d_window_attn_bwd(const float* q, const float* k, const float* v, int32_t ldq, int32_t ldk, int32_t ldv,
@@ -125,11 +136,89 @@ int seg3d_window_attn_bwd(const float* q, const float* k, const float* v, int32_
         if (workspace_bytes < attn_fused_bwd_workspace_bytes(m, n_tiles, n_qgroups, heads, dh)) return SEG3D_EWORKSPACE;
         return attn_fused_bwd_launch(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, tile_item, n_tiles,
                                      qg_item, n_qgroups, m, heads, dh, tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau,
-                                     workspace, drop, as_stream(stream));
+                                     workspace, drop, as_stream(stream), attn::kShared);
     }
     if (workspace_bytes < attn_small_blocks(n_tiles) * sizeof(float)) return SEG3D_EWORKSPACE;
     return attn_small_bwd_launch(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, tile_item, n_tiles, heads,
-                                 dh, tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, workspace, drop, as_stream(stream));
+                                 dh, tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, workspace, drop, as_stream(stream),
+                                 attn::kShared);
+}
+
+// ---- per-head tau and scaled-dot-product modes (cosine_msa.py:156-160 with non_shared_tau=True; :163-165).  The head
+// geometries, the choice of kernels (small_fwd_runs, bwd_path) and the schedule are those of the entries above; one tau
+// through these entries runs the shared-tau kernels themselves.
+size_t seg3d_window_attn_workspace_bytes_modes(int64_t m, int32_t n_tiles, int32_t heads, int32_t dh, int32_t mode,
+                                               int32_t n_tau) {
+    if (m < 0 || heads <= 0 || n_tiles < 0 || attn_kernel_mode(mode, n_tau, heads) < 0) return 0;
+    size_t bwd = 0;
+    switch (bwd_path(heads, dh)) {
+        case 0: bwd = attn_fused_bwd_workspace_bytes(m, n_tiles, n_tiles, heads, dh); break;  // one tau slot per wave in every mode
+        case 1: bwd = attn_small_blocks(n_tiles) * (n_tau > 1 ? n_tau : 1) * sizeof(float); break;  // per (tile, head)
+        default: return 0;
+    }
+    return bwd + 256;
+}
+
+int seg3d_window_attn_fwd_modes(const float* q, const float* k, const float* v, int32_t ldq, int32_t ldk, int32_t ldv,
+                                const int32_t* tok, const int32_t* win_start, const int32_t* win_count,
+                                const int32_t* tile_item, int32_t n_tiles, const int32_t* qg_item, int32_t n_qgroups, int64_t m,
+                                int32_t n_windows, int32_t heads, int32_t dh, int32_t mode, const float* tau, int32_t n_tau,
+                                float tau_min, float dropout_p, uint64_t dropout_seed, float* out, float* lse, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    (void)workspace;
+    (void)workspace_bytes;
+    const int am = attn_kernel_mode(mode, n_tau, heads);
+    if (am < 0 || (mode == SEG3D_ATTN_DOT) != (tau == nullptr)) return SEG3D_EINVAL;
+    if (m == 0 || n_windows == 0 || n_tiles == 0 || n_qgroups == 0) return SEG3D_OK;
+    if (!q || !k || !v || !tok || !win_start || !win_count || !tile_item || !qg_item || m < 0 || n_windows < 0 ||
+        n_tiles < 0 || n_qgroups < 0 || heads <= 0 || heads > 16 || !out || !(dropout_p >= 0.f && dropout_p < 1.f))
+        return SEG3D_EINVAL;
+    if (!seg3d_window_attn_supported(heads, dh)) return SEG3D_EINVAL;
+    if (rows_misaligned(q, k, v, ldq, ldk, ldv)) return SEG3D_EINVAL;  // rows are gathered in 16-B pieces
+    // Per-head tau at dh 6 takes the exact-fp32 vector-ALU forward without dropout too: a head near tau_min has scores of 72 -
+    // 144 log2 units, and over 6 channels the split-bf16 score product (2^-18 per operand) puts the forward of such a head at
+    // 1.3 x its per-head bar (6.7e-4 against 5.3e-4 at tau 0.02); in fp32 it stands at a tenth of it.  The two forms tie on
+    // time without dropout (see small_fwd_runs).
+    if ((am == attn::kPerHead && attn_small_supported(heads, dh) && lse != nullptr) ||
+        small_fwd_runs(heads, dh, dropout_p, lse != nullptr))
+        return attn_small_fwd_launch(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, tile_item, n_tiles, heads, dh, tau, tau_min,
+                                     out, lse, make_dropout(dropout_p, dropout_seed), as_stream(stream), am);
+    return attn_fused_fwd_launch(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, tile_item, n_tiles, qg_item, n_qgroups,
+                                 heads, dh, tau, tau_min, out, lse, dropout_p, dropout_seed, as_stream(stream), am);
+}
+
+int seg3d_window_attn_bwd_modes(const float* q, const float* k, const float* v, int32_t ldq, int32_t ldk, int32_t ldv,
+                                const float* out, const float* dout, const float* lse, const int32_t* tok,
+                                const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int32_t n_tiles,
+                                const int32_t* qg_item, int32_t n_qgroups, int64_t m, int32_t n_windows, int32_t heads,
+                                int32_t dh, int32_t mode, const float* tau, int32_t n_tau, float tau_min, float dropout_p,
+                                uint64_t dropout_seed, float* dq, float* dk, float* dv, int32_t lddq, int32_t lddk,
+                                int32_t lddv, float* dtau, void* workspace, size_t workspace_bytes, void* stream) {
+    const int am = attn_kernel_mode(mode, n_tau, heads);
+    if (am < 0 || !(dropout_p >= 0.f && dropout_p < 1.f)) return SEG3D_EINVAL;
+    if ((mode == SEG3D_ATTN_DOT) != (tau == nullptr) || (mode == SEG3D_ATTN_DOT && dtau)) return SEG3D_EINVAL;
+    const DropoutParams drop = make_dropout(dropout_p, dropout_seed);  // same mask as the forward, given the same two values
+    if (m == 0 || n_windows == 0 || n_tiles == 0 || n_qgroups == 0) {
+        if (dtau) SEG3D_CHECK_HIP(hipMemsetAsync(dtau, 0, (size_t)n_tau * sizeof(float), as_stream(stream)));
+        return SEG3D_OK;
+    }
+    if (!q || !k || !v || !out || !dout || !lse || !tok || !win_start || !win_count || !tile_item || !qg_item || m < 0 ||
+        n_windows < 0 || n_tiles < 0 || n_qgroups < 0 || heads <= 0 || heads > 16 || !dq || !dk || !dv ||
+        (mode == SEG3D_ATTN_COSINE && !dtau) || !workspace)
+        return SEG3D_EINVAL;
+    if (rows_misaligned(q, k, v, ldq, ldk, ldv) || rows_misaligned(dq, dk, dv, lddq, lddk, lddv))
+        return SEG3D_EINVAL;  // rows are gathered / stored in 16-B pieces
+    const int path = bwd_path(heads, dh);
+    if (path < 0 || !seg3d_window_attn_supported(heads, dh)) return SEG3D_EINVAL;
+    const size_t need = path == 0 ? attn_fused_bwd_workspace_bytes(m, n_tiles, n_qgroups, heads, dh)
+                                  : attn_small_blocks(n_tiles) * (n_tau > 1 ? n_tau : 1) * sizeof(float);
+    if (workspace_bytes < need) return SEG3D_EWORKSPACE;
+    if (path == 0)
+        return attn_fused_bwd_launch(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, tile_item, n_tiles,
+                                     qg_item, n_qgroups, m, heads, dh, tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau,
+                                     workspace, drop, as_stream(stream), am);
+    return attn_small_bwd_launch(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, tile_item, n_tiles, heads,
+                                 dh, tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, workspace, drop, as_stream(stream), am);
 }
 
 }  // extern "C"

@@ -84,8 +84,10 @@ struct FwdGeo {
     static constexpr int waves(bool dropout) { return DH == 48 ? 2 : (DH == 6 && !dropout ? SEG3D_ATTN_DH6_WAVES : 3); }
 };
 
-template <int DH, bool DROPOUT>
-__global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fwd(
+// The kernel's body for one attention mode AM (attn_common.hpp): the shared-tau kernel below is its kShared instantiation,
+// the per-head-tau and dot-product kernels behind seg3d_window_attn_fwd_modes are the other two.
+template <int DH, bool DROPOUT, int AM>
+__device__ __forceinline__ void attn_fused_fwd_body(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ldq, int ldk, int ldv,
     const int32_t* __restrict__ tok, const int32_t* __restrict__ win_start, const int32_t* __restrict__ win_count,
     const int4* __restrict__ items, int n_items, int heads, const float* __restrict__ tau, float tau_min,
@@ -128,7 +130,15 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
         *item = xcd_block_item(u / hgn, gx, XG, xcd_block);  // blocks of consecutive items (one window's tiles) per XCD
         *hg = u % hgn;
     };
-    const float qscale = kLog2e / fmaxf(tau[0], tau_min);
+    // kPerHead: log2e / max(tau[h], tau_min) of every head, once per workgroup (the persistent loop reads the table: a load of
+    // tau itself per item sat in front of the query staging -- 66 -> 86 us per dh-6 layer); kDot: 1 / sqrt(dh)
+    __shared__ float qs_heads[AM == kPerHead ? 16 : 1];
+    bool all_fixed = true;  // every head under the fixed bound: the call runs the fixed-maximum form, as the shared-tau kernel does
+    if constexpr (AM == kPerHead) {
+        if (tid < heads) qs_heads[tid] = kLog2e / fmaxf(tau[tid], tau_min);  // (visible after run()'s first barrier)
+        for (int hx = 0; hx < heads; ++hx) all_fixed = all_fixed && kLog2e / fmaxf(tau[hx], tau_min) <= 40.0f;  // (uniform)
+    }
+    const float qscale = AM == kDot ? kLog2e * __builtin_amdgcn_rsqf((float)DH) : kLog2e / fmaxf(tau[0], tau_min);
     // every score is <= qscale; p = exp2(s - qscale) >= 2^(-2 qscale) must stay a normal float
     const bool fixed_max = qscale <= 40.0f;
 
@@ -174,7 +184,7 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
                 float ss = 0.f;
 #pragma unroll
                 for (int d = 0; d < DH; ++d) ss = fmaf(reg[hh * DH + d], reg[hh * DH + d], ss);
-                const float r = scale * inv_norm(ss);
+                const float r = AM == kDot ? scale : scale * inv_norm(ss);
                 uint32_t hi[DHS / 2], lo[DHS / 2];
 #pragma unroll
                 for (int i = 0; i < DHS / 2; ++i) {
@@ -194,7 +204,7 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
 #pragma unroll
             for (int d = 0; d < CT; ++d) ss = fmaf(reg[d], reg[d], ss);
             ss = quad_sum(ss);  // the 4 threads of a row hold a quarter of the head each
-            const float r = scale * inv_norm(ss);
+            const float r = AM == kDot ? scale : scale * inv_norm(ss);
             char* p = row_dst + (st_part * CT) * 2;
 #pragma unroll
             for (int i = 0; i < CT / 2; ++i) {
@@ -337,12 +347,18 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
             const int n_q = min(QT * 32, n - q_base);  // its queries
             if (j > 0 && (j & (kDescRing / 2 - 1)) == 0) fill_desc(j + kDescRing / 2, kDescRing / 2);  // refill the dead half
 
+            // kPerHead: the scale of the head this thread stages (its quarter of a wide head / its own narrow head) and of the
+            // head this wave multiplies; in a call with a sharp head the fixed bound holds or not head by head (wave-uniform)
+            const float qs_st = AM == kPerHead ? qs_heads[h0 + (C::kNarrow ? st_part : 0)] : qscale;
+            const float qs_w = AM == kPerHead ? qs_heads[h0 + hh] : qscale;
+            const bool fixed_w = qs_w <= 40.0f;
+
             // ---- (A) park the query image and the first key tile
 #pragma unroll
             for (int p = 0; p < QP; ++p) {
                 if (q_role && (p == 0 || n_q > 64)) {
                     const int row = q_row0 + 64 * p;
-                    store_norm(q_reg[p], qscale, q_lds + row * QRS, F::kQPlane);
+                    store_norm(q_reg[p], qs_st, q_lds + row * QRS, F::kQPlane);
                     if (st_part == 0) qtok_lds[row] = q_base + row < n ? q_tok[p] : -1;
                 }
             }
@@ -366,7 +382,7 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
             uint32_t drop_row[2];
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj) {
-                m_run[jj] = -INFINITY;
+                m_run[jj] = (AM == kPerHead && fixed_w) ? qs_w : -INFINITY;
                 l_run[jj] = 0.f;
                 token[jj] = -1;
                 drop_row[jj] = 0u;
@@ -439,7 +455,7 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
                     for (int jj = 0; jj < 2; ++jj) {
                         if (jj == 1 && !two) break;
                         float sc[8];
-                        const float init = FIXED ? -qscale : 0.f;
+                        const float init = FIXED ? -qs_w : 0.f;
 #pragma unroll
                         for (int u = 0; u < 2; ++u) {
                             f32x4 acc = {init, init, init, init};
@@ -453,12 +469,16 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
 #pragma unroll
                             for (int i = 0; i < 8; ++i) sc[i] = __builtin_amdgcn_exp2f(sc[i]);
                         } else {
-                            float tmax = fmaxf(fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3])), fmaxf(fmaxf(sc[4], sc[5]), fmaxf(sc[6], sc[7])));
-                            tmax = fmaxf(tmax, __shfl_xor(tmax, 16, SEG3D_WAVE));
-                            tmax = fmaxf(tmax, __shfl_xor(tmax, 32, SEG3D_WAVE));
-                            const float m_new = fmaxf(m_run[jj], tmax);
-                            alpha = __builtin_amdgcn_exp2f(m_run[jj] - m_new);
-                            m_run[jj] = m_new;
+                            float m_new = m_run[jj];
+                            // (kPerHead: a head under the fixed bound keeps m_run = its bound and skips the maximum, wave-uniform)
+                            if (AM != kPerHead || !fixed_w) {
+                                float tmax = fmaxf(fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3])), fmaxf(fmaxf(sc[4], sc[5]), fmaxf(sc[6], sc[7])));
+                                tmax = fmaxf(tmax, __shfl_xor(tmax, 16, SEG3D_WAVE));
+                                tmax = fmaxf(tmax, __shfl_xor(tmax, 32, SEG3D_WAVE));
+                                m_new = fmaxf(m_run[jj], tmax);
+                                alpha = __builtin_amdgcn_exp2f(m_run[jj] - m_new);
+                                m_run[jj] = m_new;
+                            }
 #pragma unroll
                             for (int i = 0; i < 8; ++i) sc[i] = __builtin_amdgcn_exp2f(sc[i] - m_new);
                         }
@@ -489,7 +509,9 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
                             f32x4 acc = o_acc[jj][b];
-                            if constexpr (!FIXED) acc = acc * alpha;
+                            if constexpr (!FIXED) {
+                                if (AM != kPerHead || !fixed_w) acc = acc * alpha;
+                            }
 #ifdef SEG3D_ATTN_PV2  // (experiment, not shipped: P . V with two products -- p's low half dropped)
                             acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v_lo[b], p_hi, acc, 0, 0, 0);
                             o_acc[jj][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v_hi[b], p_hi, acc, 0, 0, 0);
@@ -549,7 +571,7 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
                             if (d + 3 < DH) *reinterpret_cast<f32x2*>(op + d + 2) = (f32x2){o[2], o[3]};
                         }
                     }
-                    const float mx = FIXED ? qscale : m_run[jj];
+                    const float mx = FIXED ? qs_w : m_run[jj];
                     if (lse && g == 0) lse[(int64_t)token[jj] * heads + h] = (mx + __builtin_amdgcn_logf(l)) * kLn2;
                 }
             }
@@ -557,8 +579,15 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
             cur = nxt;
         }
     };
-    if (fixed_max) run(std::true_type{});
-    else run(std::false_type{});
+    if constexpr (AM == kShared) {
+        if (fixed_max) run(std::true_type{});
+        else run(std::false_type{});
+    } else if constexpr (AM == kPerHead) {  // a call with a sharp head decides per head inside
+        if (all_fixed) run(std::true_type{});
+        else run(std::false_type{});
+    } else {  // kDot has no bound
+        run(std::false_type{});
+    }
 #ifdef SEG3D_ATTN_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ASTAMP(6);
@@ -569,6 +598,27 @@ __global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fw
         for (int i = 0; i < 8; ++i) o[i] = st_acc[i];
     }
 #endif
+}
+
+template <int DH, bool DROPOUT>
+__global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fwd(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ldq, int ldk, int ldv,
+    const int32_t* __restrict__ tok, const int32_t* __restrict__ win_start, const int32_t* __restrict__ win_count,
+    const int4* __restrict__ items, int n_items, int heads, const float* __restrict__ tau, float tau_min,
+    float* __restrict__ out, float* __restrict__ lse, DropoutParams drop, int xcd_groups, int xcd_block) {
+    attn_fused_fwd_body<DH, DROPOUT, kShared>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, items, n_items, heads, tau,
+                                              tau_min, out, lse, drop, xcd_groups, xcd_block);
+}
+
+// per-head tau (AM = kPerHead) and scaled dot product (AM = kDot: tau is not read)
+template <int DH, bool DROPOUT, int AM>
+__global__ __launch_bounds__(256, FwdGeo<DH>::waves(DROPOUT)) void attn_fused_fwd_modes(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ldq, int ldk, int ldv,
+    const int32_t* __restrict__ tok, const int32_t* __restrict__ win_start, const int32_t* __restrict__ win_count,
+    const int4* __restrict__ items, int n_items, int heads, const float* __restrict__ tau, float tau_min,
+    float* __restrict__ out, float* __restrict__ lse, DropoutParams drop, int xcd_groups, int xcd_block) {
+    attn_fused_fwd_body<DH, DROPOUT, AM>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, items, n_items, heads, tau, tau_min,
+                                         out, lse, drop, xcd_groups, xcd_block);
 }
 
 // The forward's schedule for one call: one round of resident workgroups (persistent): CUs x workgroups per CU, or fewer
@@ -610,18 +660,28 @@ template <int DH>
 int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
            const int32_t* win_start, const int32_t* win_count, const int4* tile_item, int n_tiles, const int4* chunk_item,
            int n_chunks, int heads, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-           hipStream_t st) {
+           hipStream_t st, int am = kShared) {
     using C = Cfg<DH>;
     const int4* items = C::kNarrow ? tile_item : chunk_item;
     const FwdSchedule s = fwd_schedule<DH>(n_tiles, n_chunks, heads, drop.threshold != 0);
     const int n_items = s.n_items, xg = s.xg, xb = s.xb;
     const dim3 grid((unsigned)s.grid);
-    if (drop.threshold)
+#define SEG3D_FWD_MODE(DROP, AM)                                                                                                   \
+    hipLaunchKernelGGL((attn_fused_fwd_modes<DH, DROP, AM>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, tok, win_start,       \
+                       win_count, items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb)
+    if (am == kPerHead) {
+        if (drop.threshold) SEG3D_FWD_MODE(true, kPerHead);
+        else SEG3D_FWD_MODE(false, kPerHead);
+    } else if (am == kDot) {
+        if (drop.threshold) SEG3D_FWD_MODE(true, kDot);
+        else SEG3D_FWD_MODE(false, kDot);
+    } else if (drop.threshold)
         hipLaunchKernelGGL((attn_fused_fwd<DH, true>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, tok, win_start, win_count,
                            items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb);
     else
         hipLaunchKernelGGL((attn_fused_fwd<DH, false>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, tok, win_start, win_count,
                            items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb);
+#undef SEG3D_FWD_MODE
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }
@@ -648,15 +708,15 @@ bool attn_fused_supported(int heads, int dh) {
 int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
                           const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles,
                           const int32_t* chunk_item, int n_chunks, int heads, int dh, const float* tau, float tau_min,
-                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st) {
+                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st, int am) {
     const DropoutParams drop = make_dropout(dropout_p, seed);
     const int4* ti = reinterpret_cast<const int4*>(tile_item);
     const int4* ci = reinterpret_cast<const int4*>(chunk_item);
     switch (dh) {
-        case 6: return launch<6>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st);
-        case 12: return launch<12>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st);
-        case 24: return launch<24>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st);
-        case 48: return launch<48>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st);
+        case 6: return launch<6>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
+        case 12: return launch<12>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
+        case 24: return launch<24>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
+        case 48: return launch<48>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
         default: return SEG3D_EINVAL;
     }
 }

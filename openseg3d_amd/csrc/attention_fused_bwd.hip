@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "attn_fused.hpp"
+#include "wave_ops.hpp"
 
 #ifdef SEG3D_ATTN_STAMP
 // Diagnostic build only (tools/probes/attn_bwd_stamps.py): per-wave s_memtime (100 MHz) spans of the backward passes:
@@ -131,8 +132,18 @@ __device__ __forceinline__ void through_normalise_lds(const char* img_row, int p
 template <int DH, int MODE>
 constexpr int kBwdWaves = (DH <= 24 && MODE == 0) ? SEG3D_BWD_Q_WAVES : (DH == 48 && MODE == 1) ? 1 : (DH == 48) ? SEG3D_BWD_Q48_WAVES : 2;
 
-template <int DH, int MODE>
-__global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
+// (the dot-product pass Q spills 300 - 490 bytes per thread at the three waves of the cosine pass Q -- without the
+// normalisation in front of the staging stores the allocator keeps more of a tile's rows in flight; two waves are spill-free)
+template <int DH, int PM>
+constexpr int kBwdModeWaves = (PM == 2 * kDot && DH <= 24) ? 2 : kBwdWaves<DH, (PM & 1)>;
+
+// PM = pass + 2 x attention mode (attn_common.hpp): PM 0 / 1 are the shared-tau passes Q / KV as they always were, 2 / 3 the
+// per-head-tau passes, 4 / 5 the dot-product passes -- further instantiations, no run-time branch on the mode.
+// kPerHead: a wave works on ONE head, so its scales, its clamp and its tau partial are that head's (tau_part keeps one slot
+// per wave; tau_reduce_heads adds the slots of a head).  kDot: no normalisation on either side, dS goes straight to q and k,
+// nothing is written for tau.
+template <int DH, int PM>
+__global__ __launch_bounds__(256, (kBwdModeWaves<DH, PM>)) void attn_fused_bwd(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, int ldq, int ldk, int ldv,
     const float* __restrict__ out, const float* __restrict__ dout, const float* __restrict__ lse,
     const int32_t* __restrict__ tok, const int32_t* __restrict__ win_start, const int32_t* __restrict__ win_count,
@@ -140,6 +151,7 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
     int lddq, float* __restrict__ dk, int lddk, float* __restrict__ dv, int lddv, float* __restrict__ tau_part,
     float* __restrict__ delta_buf, DropoutParams drop, int xcd_block) {
     using C = Cfg<DH>;
+    constexpr int MODE = PM & 1, AM = PM >> 1;
     constexpr int HG = C::HG, QT = C::QT, DHS = C::DHS, KS = C::KS, VW = C::VW;
     constexpr int KRS = C::KRS, VRS = C::VRS, CT = C::CT;
     constexpr int NBQ = (DH + 15) / 16;  // 16-row d-blocks of a gradient
@@ -184,7 +196,7 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
     const int gx = (int)blockIdx.x % XG, gu = (int)blockIdx.x / XG;
     const int item_i = xcd_block_item(gu / hgn, gx, XG, xcd_block);  // blocks of consecutive items per XCD (attn_fused.hpp)
     if (item_i >= n_items) {  // (padding of the last group)
-        if (MODE == 0 && tau_part && lane == 0) tau_part[(size_t)blockIdx.x * 4 + wave] = 0.f;
+        if (MODE == 0 && AM != kDot && tau_part && lane == 0) tau_part[(size_t)blockIdx.x * 4 + wave] = 0.f;
         return;
     }
     const int4 item = items[item_i];  // {window, tile / chunk, first token slot, tokens}: one round trip less in front of the gathers
@@ -193,8 +205,8 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
     const int n_t = (n + 31) >> 5;  // 32-token tiles of the window (streamed and stationary alike)
     const int h0 = (gu % hgn) * HG;
     const int c_all = heads * DH;
-    const float tau_c = fmaxf(tau[0], tau_min);
-    const float qscale = kLog2e / tau_c;
+    const float tau_c = AM == kDot ? 1.0f : fmaxf(tau[0], tau_min);
+    const float qscale = AM == kDot ? kLog2e * __builtin_amdgcn_rsqf((float)DH) : kLog2e / tau_c;
 
     // ---------------------------------------------------------------- staging role of this thread
     const int st_which = tid >> 7;  // 0: image A (normalised: K^ or Q~), 1: image B (V or dO)
@@ -202,7 +214,9 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
     const float* st_src = MODE == 0 ? (st_which == 0 ? k : v) : (st_which == 0 ? q : dout);
     const int st_ld = MODE == 0 ? (st_which == 0 ? ldk : ldv) : (st_which == 0 ? ldq : c_all);
     const int st_col = C::kNarrow ? (h0 + C::HPT * st_part) * DH : h0 * DH + st_part * CT;
-    const float st_scale = MODE == 0 ? 1.0f : qscale;
+    // kPerHead: the scale of the head this thread stages (its own narrow head / its quarter of the workgroup's wide head)
+    const float qscale_st = AM == kPerHead ? kLog2e / fmaxf(tau[h0 + (C::kNarrow ? st_part : 0)], tau_min) : qscale;
+    const float st_scale = MODE == 0 ? 1.0f : qscale_st;
     // Dropout's 1 / keep factor rides on dO (image B of pass KV, the stationary dO image of pass Q): dP' = dP / keep and
     // dV = (keep-masked P)^T dO', so the elementwise part of both passes only SELECTS (no per-element factor)
     const float st_bscale = (MODE == 1 && drop.threshold) ? drop.inv_keep : 1.0f;
@@ -245,7 +259,7 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
                 float ss = 0.f;
 #pragma unroll
                 for (int d = 0; d < DH; ++d) ss = fmaf(st_reg[d], st_reg[d], ss);
-                const float r = st_scale * inv_norm(ss);
+                const float r = AM == kDot ? st_scale : st_scale * inv_norm(ss);
                 uint32_t hi[DHS / 2], lo[DHS / 2];
 #pragma unroll
                 for (int i = 0; i < DHS / 2; ++i) {
@@ -264,7 +278,7 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
 #pragma unroll
                 for (int d = 0; d < CT; ++d) ss = fmaf(st_reg[d], st_reg[d], ss);
                 ss = quad_sum(ss);
-                const float r = st_scale * inv_norm(ss);
+                const float r = AM == kDot ? st_scale : st_scale * inv_norm(ss);
                 char* p = dst + (st_part * CT) * 2;
 #pragma unroll
                 for (int i = 0; i < CT / 2; ++i) {
@@ -334,6 +348,8 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
     const int st_tile = C::kNarrow ? 0 : unit;
     const int hh = C::kNarrow ? unit : 0;
     const int h = h0 + hh;
+    const float tau_w = AM == kPerHead ? fmaxf(tau[h], tau_min) : tau_c;  // the wave's own head
+    const float qscale_w = AM == kPerHead ? kLog2e / tau_w : qscale;
     const int s0 = (item.y * QT + st_tile) * 32;  // first stationary token of this wave
     const bool active = st_tile < n_st_here;      // wave-uniform
     const bool two = n - s0 > 16;                 // the tile's second 16-token group exists (wave-uniform)
@@ -396,8 +412,8 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
                     float ss = 0.f;
 #pragma unroll
                     for (int d = 0; d < DH; ++d) ss = fmaf(ra[p][d], ra[p][d], ss);
-                    const float rn = inv_norm(ss);
-                    const float r = (MODE == 0 ? qscale : 1.0f) * rn;
+                    const float rn = AM == kDot ? 1.0f : inv_norm(ss);
+                    const float r = (MODE == 0 ? qscale_st : 1.0f) * rn;
                     snrm_lds[row * HG + st_part] = rn;
                     uint32_t hi[DHS / 2], lo[DHS / 2], bhi[DHS / 2], blo[DHS / 2];
 #pragma unroll
@@ -421,8 +437,8 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
 #pragma unroll
                     for (int d = 0; d < CT; ++d) ss = fmaf(ra[p][d], ra[p][d], ss);
                     ss = quad_sum(ss);
-                    const float rn = inv_norm(ss);
-                    const float r = (MODE == 0 ? qscale : 1.0f) * rn;
+                    const float rn = AM == kDot ? 1.0f : inv_norm(ss);
+                    const float r = (MODE == 0 ? qscale_st : 1.0f) * rn;
                     if (st_part == 0) snrm_lds[row] = rn;
 #pragma unroll
                     for (int i = 0; i < CT / 2; ++i) {
@@ -483,6 +499,8 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
 
     f32x4 acc0[2][NBQ], acc1[MODE == 1 ? 2 : 1][NBQ];  // MODE 0: dQ^^T; MODE 1: dK^^T (acc0) and dV^T (acc1)
     f32x2 tau2[2] = {{0.f, 0.f}, {0.f, 0.f}};
+    // kPerHead: sum_j dS and sum_j P (S - L) of the lane's queries, for the row constant of the tau gradient (epilogue)
+    float tb[2] = {0.f, 0.f}, tm[2] = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -605,6 +623,10 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
                     // exp, lies between the row's mean and its largest score, so the terms that carry weight stay O(log2 n)
                     // at every tau, where S itself reaches log2e / tau = 72 at tau 0.02
                     if (MODE == 0) tau2[j] = __builtin_elementwise_fma(ds2, e2 + (f32x2){log2n, log2n}, tau2[j]);
+                    if constexpr (MODE == 0 && AM == kPerHead) {
+                        tb[j] += ds2[0] + ds2[1];
+                        tm[j] = fmaf(p2[0], e2[0], fmaf(p2[1], e2[1], tm[j]));
+                    }
                     else pv[u * 2 + r2] = pk2;          // dV = (D P)^T dO
                 }
             }
@@ -696,7 +718,7 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
     // ---------------------------------------------------------------- epilogue
     float* tau_slot = tau_part ? tau_part + (size_t)blockIdx.x * 4 + wave : nullptr;
     if (!active) {
-        if (MODE == 0 && lane == 0) *tau_slot = 0.f;
+        if (MODE == 0 && AM != kDot && lane == 0) *tau_slot = 0.f;
         return;
     }
     float tau_sum = 0.f;
@@ -708,12 +730,31 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
         const int srow = st_tile * 32 + 16 * j + c16;  // the lane's row of the stationary images (all rows were staged)
         const char* img_row = sa_lds + srow * SRS + hh * DHS * 2;
         const float rinv = snrm_lds[srow * HG + hh];
-        if constexpr (MODE == 0) {
-            const float inv_tau = 1.0f / tau_c;
+        if constexpr (AM == kDot) {
+            // S2 = Q~.K with Q~ = q log2e / sqrt(dh): dq = K^T dS / sqrt(dh), dk = Q~^T dS ln2 -- no normalisation to go through
+            const float fac = MODE == 0 ? __builtin_amdgcn_rsqf((float)DH) : kLn2;
+#pragma unroll
+            for (int b = 0; b < NBQ; ++b) acc0[j][b] = acc0[j][b] * fac;
+        } else if constexpr (MODE == 0) {
+            const float inv_tau = 1.0f / tau_w;
 #pragma unroll
             for (int b = 0; b < NBQ; ++b) acc0[j][b] = acc0[j][b] * inv_tau;
             if (valid) tau_sum += tau2[j][0] + tau2[j][1];
-            through_normalise_lds<DH, DHS, NBQ>(img_row, kSPlane, 1.0f / qscale, rinv, g, acc0[j]);
+            if constexpr (AM == kPerHead) {
+                // One head's gradient stands alone, with nothing of the other heads to hide its error in: move the row constant
+                // from log(mean exp) to the row's P-weighted mean score, c = L + sum_j P (S - L), after the fact --
+                // sum_j dS (S - c) = sum_j dS (S - L + log2 n) - (sum_j dS) (log2 n + sum_j P (S - L)).  With that constant
+                // sum_j P (S - c) = 0: an error of delta = <dO, O> (it carries the forward's split-bf16 error) or of the row
+                // sum no longer reaches dtau in first order, and the noise of the recomputed P is weighted by the spread of
+                // the scores that carry probability instead of by log2 n (a sharp row: 1 - 2 bits instead of 9).
+                float b = tb[j], mm = tm[j];  // (the 4 lanes of a query column hold a quarter each)
+                b += __shfl_xor(b, 16, SEG3D_WAVE);
+                b += __shfl_xor(b, 32, SEG3D_WAVE);
+                mm += __shfl_xor(mm, 16, SEG3D_WAVE);
+                mm += __shfl_xor(mm, 32, SEG3D_WAVE);
+                if (valid && g == 0) tau_sum -= b * (log2n + mm);
+            }
+            through_normalise_lds<DH, DHS, NBQ>(img_row, kSPlane, 1.0f / qscale_w, rinv, g, acc0[j]);
         } else {
 #pragma unroll
             for (int b = 0; b < NBQ; ++b) acc0[j][b] = acc0[j][b] * kLn2;  // Q~ = q_hat log2e / tau  ->  q_hat / tau = Q~ ln2
@@ -742,10 +783,10 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
             }
         }
     }
-    if constexpr (MODE == 0) {
+    if constexpr (MODE == 0 && AM != kDot) {
         // d/dtau: s_nat = s2 ln2 = c / tau  ->  dL/dtau = -sum(ds s_nat) / tau   (zero while tau is clamped)
         for (int off = 32; off > 0; off >>= 1) tau_sum += __shfl_xor(tau_sum, off, SEG3D_WAVE);
-        if (lane == 0) *tau_slot = tau[0] > tau_min ? -tau_sum * kLn2 / tau_c : 0.f;
+        if (lane == 0) *tau_slot = tau[AM == kPerHead ? h : 0] > tau_min ? -tau_sum * kLn2 / tau_w : 0.f;
     }
 #ifdef SEG3D_ATTN_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -764,6 +805,23 @@ __global__ __launch_bounds__(256, (kBwdWaves<DH, MODE>)) void attn_fused_bwd(
         o[3] = (unsigned long long)n_t;
     }
 #endif
+}
+
+// dtau[h] = sum of the partials of the waves that worked on head h, in a fixed order (block = head).  Pass Q's block b belongs to
+// head group (b / 8) % hgn (attn_fused_bwd); a narrow group's wave w is head w of the group, a wide group is one head.
+__global__ __launch_bounds__(256) void tau_reduce_heads(const float* __restrict__ part, int n_blocks, int hgn, int narrow,
+                                                        float* __restrict__ dtau) {
+    const int h = blockIdx.x, hg = narrow ? h >> 2 : h;
+    const int per = narrow ? 8 : 32;             // slots of the head per group of 8 blocks
+    const int count = n_blocks / (8 * hgn) * per;
+    float v = 0.f;
+    for (int e = threadIdx.x; e < count; e += 256) {
+        const int i = e / per, r = e % per;       // i-th group of 8 blocks of this head group, slot r of the head in it
+        const int slot = narrow ? ((hg + i * hgn) * 8 + r) * 4 + (h & 3) : (hg + i * hgn) * 32 + r;
+        v += part[slot];
+    }
+    v = block_sum<256>(v);
+    if (threadIdx.x == 0) dtau[h] = v;
 }
 
 // dtau = sum of the per-wave partials in a fixed order
@@ -794,12 +852,34 @@ int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int
            const float* lse, const int32_t* tok, const int32_t* win_start, const int32_t* win_count, const int4* tile_item,
            int n_tiles, const int4* chunk_item, int n_chunks, int heads, const float* tau, float tau_min, float* dq, float* dk,
            float* dv, int lddq, int lddk, int lddv, float* dtau, float* tau_part, float* delta_buf, const DropoutParams& drop,
-           hipStream_t st) {
+           hipStream_t st, int am) {
     using C = Cfg<DH>;
     const int4* items = C::kNarrow ? tile_item : chunk_item;
     const int n_items = C::kNarrow ? n_tiles : n_chunks;
     const int xb = xcd_block_items(C::kNarrow, n_items);
     const dim3 grid((unsigned)attn_fused_bwd_blocks(n_tiles, n_chunks, heads, DH));
+#define SEG3D_BWD_MODE(PASS, AM, PART)                                                                                            \
+    hipLaunchKernelGGL((attn_fused_bwd<DH, PASS + 2 * AM>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, out, dout, lse, tok, \
+                       win_start, win_count, items, n_items, heads, tau, tau_min, dq, lddq, dk, lddk, dv, lddv, PART, delta_buf,  \
+                       drop, xb)
+    if (am == kPerHead) {
+        SEG3D_BWD_MODE(0, kPerHead, tau_part);
+        SEG3D_CHECK_LAUNCH();
+        hipLaunchKernelGGL(tau_reduce_heads, dim3((unsigned)heads), dim3(256), 0, st, tau_part, (int)grid.x, heads / C::HG,
+                           C::kNarrow ? 1 : 0, dtau);
+        SEG3D_CHECK_LAUNCH();
+        SEG3D_BWD_MODE(1, kPerHead, nullptr);
+        SEG3D_CHECK_LAUNCH();
+        return SEG3D_OK;
+    }
+    if (am == kDot) {
+        SEG3D_BWD_MODE(0, kDot, nullptr);
+        SEG3D_CHECK_LAUNCH();
+        SEG3D_BWD_MODE(1, kDot, nullptr);
+        SEG3D_CHECK_LAUNCH();
+        return SEG3D_OK;
+    }
+#undef SEG3D_BWD_MODE
     hipLaunchKernelGGL((attn_fused_bwd<DH, 0>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start,
                        win_count, items, n_items, heads, tau, tau_min, dq, lddq, dk, lddk, dv, lddv, tau_part, delta_buf, drop, xb);
     SEG3D_CHECK_LAUNCH();
@@ -842,7 +922,7 @@ int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ld
                           const int32_t* win_count, const int32_t* tile_item, int n_tiles, const int32_t* chunk_item,
                           int n_chunks, int64_t m, int heads, int dh, const float* tau, float tau_min, float* dq, float* dk,
                           float* dv, int lddq, int lddk, int lddv, float* dtau, void* workspace, const DropoutParams& drop,
-                          hipStream_t st) {
+                          hipStream_t st, int am) {
     (void)m;
     const int4* ti = reinterpret_cast<const int4*>(tile_item);
     const int4* ci = reinterpret_cast<const int4*>(chunk_item);
@@ -851,7 +931,7 @@ int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ld
 #define SEG3D_FB(D)                                                                                                        \
     case D:                                                                                                                \
         return launch<D>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, \
-                         tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, delta_buf, drop, st)
+                         tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, delta_buf, drop, st, am)
     switch (dh) {
         SEG3D_FB(6);
         SEG3D_FB(12);

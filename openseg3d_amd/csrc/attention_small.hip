@@ -13,6 +13,7 @@
 // with the gradient through x_hat = x / max(|x|, eps) applied to the thread's own vector at the end.
 // Work items are the (window, 32-token tile) list of seg3d_window_partition; block = 32 tokens x heads threads.
 #include "attn_common.hpp"
+#include "wave_ops.hpp"
 
 namespace {
 
@@ -94,6 +95,13 @@ __device__ __forceinline__ float normalise(Vec<DH>* x, float scale_to) {
     return len;
 }
 
+// what a kernel stages of a raw row in attention mode AM: the normalised row (x scale_to), or in kDot the row itself (x scale_to)
+template <int DH, int AM>
+__device__ __forceinline__ void stage_vec(Vec<DH>* x, float scale_to) {
+    if constexpr (AM == kDot) scale<DH>(scale_to, x);
+    else normalise<DH>(x, scale_to);
+}
+
 // gradient through x_hat = x / max(|x|, eps): g (w.r.t. x_hat) -> g (w.r.t. x), cosine_msa.py:152-153
 template <int DH>
 __device__ __forceinline__ void through_normalise(const Vec<DH>& x_raw, Vec<DH>* g) {
@@ -123,13 +131,18 @@ constexpr int kMaxHeads = 16;
 // are bounded by log2e / tau: that bound is the fixed softmax maximum while exp2(-2 bound) stays a normal float (tau > ~0.036),
 // otherwise the running-maximum form -- a block-uniform choice on the device scalar tau.  The row sum is taken BEFORE the
 // dropout factor (cosine_msa.py:172-176: softmax, then F.dropout, then attn @ v).
-template <int DH, int THREADS>
-__global__ __launch_bounds__(THREADS, 8) void attn_small_fwd(const float* __restrict__ q, const float* __restrict__ k,
+// Attention mode AM (attn_common.hpp): kShared is the kernel as it was; kPerHead takes tau[h] of the thread's own head (the fixed bound
+// holds or not per head: a half-wave choice); kDot stages raw rows, scales q by log2e / sqrt(dh) and always runs the maximum.
+// TM = threads of the workgroup (256 / 512) + the attention mode: <6, 256> and <6, 512> are the kernels as they always were,
+// <6, 256 + kPerHead> ... further instantiations (no run-time branch on the mode).
+template <int DH, int TM>
+__global__ __launch_bounds__((TM & ~3), 8) void attn_small_fwd(const float* __restrict__ q, const float* __restrict__ k,
                                                       const float* __restrict__ v, int ldq, int ldk, int ldv,
                                                       const int32_t* __restrict__ tok, const int32_t* __restrict__ win_start,
                                                       const int32_t* __restrict__ win_count, const int4* __restrict__ tile_item,
                                                       int heads, const float* __restrict__ tau, float tau_min,
                                                       float* __restrict__ out, float* __restrict__ lse, DropoutParams drop) {
+    constexpr int AM = TM & 3;
     extern __shared__ float smem[];
     const int c = heads * DH;
     float* kbuf = smem;
@@ -139,13 +152,13 @@ __global__ __launch_bounds__(THREADS, 8) void attn_small_fwd(const float* __rest
     const int n = item.w, start = item.z;
     const int qi = item.y * kTile + i;
     const int32_t qtok = qi < n ? tok[start + qi] : -1;
-    const float tau_c = fmaxf(tau[0], tau_min);
-    const float bound = kLog2e / tau_c;  // every score (log2 domain) is <= bound
-    const bool fixed_max = bound <= 40.0f;
+    const float tau_c = AM == kDot ? 1.0f : fmaxf(tau[AM == kPerHead ? h : 0], tau_min);
+    const float bound = AM == kDot ? kLog2e * __builtin_amdgcn_rsqf((float)DH) : kLog2e / tau_c;  // every score (log2 domain) is <= bound
+    const bool fixed_max = AM == kDot ? false : bound <= 40.0f;
     Vec<DH> qn = zero_vec<DH>(), acc = zero_vec<DH>();
     if (qtok >= 0) {
         qn = load_vec<DH>(q + (int64_t)qtok * ldq + h * DH);
-        normalise<DH>(&qn, bound);
+        stage_vec<DH, AM>(&qn, bound);
     }
     float l = 0.f, mx = fixed_max ? bound : -INFINITY;
     const uint32_t row_state = drop.threshold ? dropout_row_state(dropout_head_state(drop, item.x, h), qi) : 0u;
@@ -164,7 +177,7 @@ __global__ __launch_bounds__(THREADS, 8) void attn_small_fwd(const float* __rest
         __syncthreads();
         {
             Vec<DH> kk = k_next;
-            normalise<DH>(&kk, 1.0f);
+            stage_vec<DH, AM>(&kk, 1.0f);
             store_vec<DH>(kbuf + i * c + h * DH, kk);
             store_vec<DH>(vbuf + i * c + h * DH, v_next);
         }
@@ -206,8 +219,10 @@ __global__ __launch_bounds__(THREADS, 8) void attn_small_fwd(const float* __rest
 }
 
 // ------------------------------------------------------------------ backward, pass Q: dq, dtau
-template <int DH, int THREADS>
-__global__ __launch_bounds__(THREADS, 2) void attn_small_bwd_q(const float* __restrict__ q, const float* __restrict__ k,
+// kPerHead: tau[h] of the thread's head; the two heads of a wave keep their sums apart (half-wave sums), one partial per
+// (tile, head).  kDot: dq = sum ds k / sqrt(dh) straight, no tau partial.
+template <int DH, int TM>
+__global__ __launch_bounds__((TM & ~3), 2) void attn_small_bwd_q(const float* __restrict__ q, const float* __restrict__ k,
                                                         const float* __restrict__ v, int ldq, int ldk, int ldv,
                                                         const float* __restrict__ out, const float* __restrict__ dout,
                                                         const float* __restrict__ lse, const int32_t* __restrict__ tok,
@@ -215,6 +230,7 @@ __global__ __launch_bounds__(THREADS, 2) void attn_small_bwd_q(const float* __re
                                                         const int4* __restrict__ tile_item, int heads,
                                                         const float* __restrict__ tau, float tau_min, float* __restrict__ dq,
                                                         int lddq, float* __restrict__ tau_part, DropoutParams drop) {
+    constexpr int AM = TM & 3;
     extern __shared__ float smem[];
     const int c = heads * DH;
     float* kbuf = smem;
@@ -225,13 +241,13 @@ __global__ __launch_bounds__(THREADS, 2) void attn_small_bwd_q(const float* __re
     const int n = item.w, start = item.z;
     const int qi = item.y * kTile + i;
     const int32_t qtok = qi < n ? tok[start + qi] : -1;
-    const float tau_c = fmaxf(tau[0], tau_min);
+    const float tau_c = AM == kDot ? 1.0f : fmaxf(tau[AM == kPerHead ? h : 0], tau_min);
     Vec<DH> q_raw = zero_vec<DH>(), qn = zero_vec<DH>(), go = zero_vec<DH>(), acc = zero_vec<DH>();
     float l2 = 0.f, delta = 0.f;
     if (qtok >= 0) {
         q_raw = load_vec<DH>(q + (int64_t)qtok * ldq + h * DH);
         qn = q_raw;
-        normalise<DH>(&qn, kLog2e / tau_c);
+        stage_vec<DH, AM>(&qn, AM == kDot ? kLog2e * __builtin_amdgcn_rsqf((float)DH) : kLog2e / tau_c);
         go = load_vec<DH>(dout + (int64_t)qtok * c + h * DH);
         const Vec<DH> oo = load_vec<DH>(out + (int64_t)qtok * c + h * DH);
         delta = dot(go, oo);
@@ -261,7 +277,7 @@ __global__ __launch_bounds__(THREADS, 2) void attn_small_bwd_q(const float* __re
         __syncthreads();
         {
             Vec<DH> kk = k_next;
-            normalise<DH>(&kk, 1.0f);
+            stage_vec<DH, AM>(&kk, 1.0f);
             store_vec<DH>(kbuf + i * c + h * DH, kk);
             store_vec<DH>(vbuf + i * c + h * DH, v_next);
         }
@@ -291,11 +307,23 @@ __global__ __launch_bounds__(THREADS, 2) void attn_small_bwd_q(const float* __re
         }
     }
     if (qtok >= 0) {
-        scale<DH>(1.0f / tau_c, &acc);
-        through_normalise<DH>(q_raw, &acc);
+        if constexpr (AM == kDot) {
+            scale<DH>(__builtin_amdgcn_rsqf((float)DH), &acc);
+        } else {
+            scale<DH>(1.0f / tau_c, &acc);
+            through_normalise<DH>(q_raw, &acc);
+        }
         store_vec<DH>(dq + (int64_t)qtok * lddq + h * DH, acc);
     } else {
         tau_acc = 0.f;
+    }
+    if constexpr (AM == kDot) {
+        return;
+    } else if constexpr (AM == kPerHead) {
+        // the 32 lanes of this head (a half-wave): xor tree 16 ... 1; one plain store per (tile, head)
+        for (int off = 16; off > 0; off >>= 1) tau_acc += __shfl_xor(tau_acc, off, SEG3D_WAVE);
+        if (i == 0) tau_part[(size_t)blockIdx.x * heads + h] = tau[h] > tau_min ? -tau_acc * kLn2 / tau_c : 0.f;
+        return;
     }
     // d/dtau: s_nat = s2 * ln2 = c / tau  ->  dL/dtau = -sum(ds * s_nat) / tau   (zero while tau is clamped)
     for (int off = 32; off > 0; off >>= 1) tau_acc += __shfl_xor(tau_acc, off, SEG3D_WAVE);
@@ -309,8 +337,8 @@ __global__ __launch_bounds__(THREADS, 2) void attn_small_bwd_q(const float* __re
 }
 
 // ------------------------------------------------------------------ backward, pass KV: dk, dv
-template <int DH, int THREADS>
-__global__ __launch_bounds__(THREADS, 3) void attn_small_bwd_kv(const float* __restrict__ q, const float* __restrict__ k,
+template <int DH, int TM>
+__global__ __launch_bounds__((TM & ~3), 3) void attn_small_bwd_kv(const float* __restrict__ q, const float* __restrict__ k,
                                                          const float* __restrict__ v, int ldq, int ldk, int ldv,
                                                          const float* __restrict__ out, const float* __restrict__ dout,
                                                          const float* __restrict__ lse, const int32_t* __restrict__ tok,
@@ -318,6 +346,7 @@ __global__ __launch_bounds__(THREADS, 3) void attn_small_bwd_kv(const float* __r
                                                          const int4* __restrict__ tile_item, int heads,
                                                          const float* __restrict__ tau, float tau_min, float* __restrict__ dk,
                                                          int lddk, float* __restrict__ dv, int lddv, DropoutParams drop) {
+    constexpr int AM = TM & 3;
     extern __shared__ float smem[];  // q~ [32][c], dO [32][c], (L, delta) [32][heads][2]
     const int c = heads * DH;
     float* qbuf = smem;
@@ -328,12 +357,12 @@ __global__ __launch_bounds__(THREADS, 3) void attn_small_bwd_kv(const float* __r
     const int n = item.w, start = item.z;
     const int kj = item.y * kTile + i;
     const int32_t ktok = kj < n ? tok[start + kj] : -1;
-    const float tau_c = fmaxf(tau[0], tau_min);
+    const float tau_c = AM == kDot ? 1.0f : fmaxf(tau[AM == kPerHead ? h : 0], tau_min);
     Vec<DH> k_raw = zero_vec<DH>(), kn = zero_vec<DH>(), vv = zero_vec<DH>(), dk_acc = zero_vec<DH>(), dv_acc = zero_vec<DH>();
     if (ktok >= 0) {
         k_raw = load_vec<DH>(k + (int64_t)ktok * ldk + h * DH);
         kn = k_raw;
-        normalise<DH>(&kn, 1.0f);
+        stage_vec<DH, AM>(&kn, 1.0f);
         vv = load_vec<DH>(v + (int64_t)ktok * ldv + h * DH);
     }
     // dropout: what does not depend on the streamed query -- the (window, head) state and the lane's key term
@@ -359,7 +388,7 @@ __global__ __launch_bounds__(THREADS, 3) void attn_small_bwd_kv(const float* __r
         __syncthreads();
         {  // stage query row t0 + i, head h (all-zero rows past n: p is masked below)
             Vec<DH> qq = q_next;
-            normalise<DH>(&qq, kLog2e / tau_c);
+            stage_vec<DH, AM>(&qq, AM == kDot ? kLog2e * __builtin_amdgcn_rsqf((float)DH) : kLog2e / tau_c);
             store_vec<DH>(qbuf + i * c + h * DH, qq);
             store_vec<DH>(gbuf + i * c + h * DH, g_next);
             *reinterpret_cast<f32x2*>(lbuf + (i * heads + h) * 2) = (f32x2){lse_next * kLog2e, dot(g_next, o_next)};
@@ -390,11 +419,20 @@ __global__ __launch_bounds__(THREADS, 3) void attn_small_bwd_kv(const float* __r
         }
     }
     if (ktok >= 0) {
-        scale<DH>(kLn2, &dk_acc);  // q~ = q_hat * log2e / tau  ->  q_hat / tau = q~ * ln2
-        through_normalise<DH>(k_raw, &dk_acc);
+        scale<DH>(kLn2, &dk_acc);  // q~ = q_hat * log2e / tau  ->  q_hat / tau = q~ * ln2  (kDot: q / sqrt(dh) = q~ * ln2)
+        if constexpr (AM != kDot) through_normalise<DH>(k_raw, &dk_acc);
         store_vec<DH>(dk + (int64_t)ktok * lddk + h * DH, dk_acc);
         store_vec<DH>(dv + (int64_t)ktok * lddv + h * DH, dv_acc);
     }
+}
+
+// dtau[h] = sum over the tiles of part[tile][h] in a fixed order (block = head)
+__global__ __launch_bounds__(256) void tau_reduce_small_heads(const float* __restrict__ part, int n_tiles, int heads,
+                                                              float* __restrict__ dtau) {
+    float v = 0.f;
+    for (int t = threadIdx.x; t < n_tiles; t += 256) v += part[(size_t)t * heads + blockIdx.x];
+    v = block_sum<256>(v);
+    if (threadIdx.x == 0) dtau[blockIdx.x] = v;
 }
 
 __global__ __launch_bounds__(1024) void tau_reduce_small(const float* __restrict__ part, int count, float* __restrict__ dtau) {
@@ -424,8 +462,30 @@ int run_small_bwd(const float* q, const float* k, const float* v, int ldq, int l
                   const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
                   const int32_t* win_count, const int4* tile_item, int n_tiles, int heads, const float* tau, float tau_min,
                   float* dq, float* dk, float* dv, int lddq, int lddk, int lddv, float* dtau, float* tau_part,
-                  const DropoutParams& drop, hipStream_t st) {
+                  const DropoutParams& drop, hipStream_t st, int am) {
     const size_t smem_q = (size_t)2 * kTile * heads * DH * sizeof(float);
+    if (am != kShared) {
+        const dim3 grid((unsigned)attn_small_blocks(n_tiles)), block(32 * heads);
+        const size_t smem_kv2 = smem_q + (size_t)kTile * heads * 2 * sizeof(float);
+#define SEG3D_SMALL_BWD_MODE(AM)                                                                                                   \
+    hipLaunchKernelGGL((attn_small_bwd_q<DH, THREADS + AM>), grid, block, smem_q, st, q, k, v, ldq, ldk, ldv, out, dout, lse,   \
+                       tok, win_start, win_count, tile_item, heads, tau, tau_min, dq, lddq, tau_part, drop);                        \
+    SEG3D_CHECK_LAUNCH();                                                                                                          \
+    if (AM == kPerHead) {                                                                                                          \
+        hipLaunchKernelGGL(tau_reduce_small_heads, dim3((unsigned)heads), dim3(256), 0, st, tau_part, n_tiles, heads, dtau);        \
+        SEG3D_CHECK_LAUNCH();                                                                                                      \
+    }                                                                                                                              \
+    hipLaunchKernelGGL((attn_small_bwd_kv<DH, THREADS + AM>), grid, block, smem_kv2, st, q, k, v, ldq, ldk, ldv, out, dout,     \
+                       lse, tok, win_start, win_count, tile_item, heads, tau, tau_min, dk, lddk, dv, lddv, drop);                   \
+    SEG3D_CHECK_LAUNCH()
+        if (am == kPerHead) {
+            SEG3D_SMALL_BWD_MODE(kPerHead);
+        } else {
+            SEG3D_SMALL_BWD_MODE(kDot);
+        }
+#undef SEG3D_SMALL_BWD_MODE
+        return SEG3D_OK;
+    }
     hipLaunchKernelGGL((attn_small_bwd_q<DH, THREADS>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem_q, st, q, k, v, ldq, ldk, ldv,
                        out, dout, lse, tok, win_start, win_count, tile_item, heads, tau, tau_min, dq, lddq, tau_part, drop);
     SEG3D_CHECK_LAUNCH();
@@ -443,10 +503,27 @@ int run_small_bwd(const float* q, const float* k, const float* v, int ldq, int l
 int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
                           const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads,
                           int dh, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-                          hipStream_t st) {
+                          hipStream_t st, int am) {
     if (dh != 6) return SEG3D_EINVAL;
     const size_t smem = (size_t)2 * kTile * heads * 6 * sizeof(float);
     if (!attn_small_supported(heads, dh)) return SEG3D_EINVAL;
+    if (am != kShared) {
+        const dim3 grid((unsigned)attn_small_blocks(n_tiles)), block(32 * heads);
+        const int4* ti = reinterpret_cast<const int4*>(tile_item);
+#define SEG3D_SMALL_FWD_MODE(T, AM)                                                                                           \
+    hipLaunchKernelGGL((attn_small_fwd<6, T + AM>), grid, block, smem, st, q, k, v, ldq, ldk, ldv, tok, win_start, win_count, \
+                       ti, heads, tau, tau_min, out, lse, drop)
+        if (am == kPerHead) {
+            if (heads <= 8) SEG3D_SMALL_FWD_MODE(256, kPerHead);
+            else SEG3D_SMALL_FWD_MODE(512, kPerHead);
+        } else {
+            if (heads <= 8) SEG3D_SMALL_FWD_MODE(256, kDot);
+            else SEG3D_SMALL_FWD_MODE(512, kDot);
+        }
+#undef SEG3D_SMALL_FWD_MODE
+        SEG3D_CHECK_LAUNCH();
+        return SEG3D_OK;
+    }
     if (heads <= 8)
         hipLaunchKernelGGL((attn_small_fwd<6, 256>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem, st, q, k, v, ldq, ldk, ldv, tok,
                            win_start, win_count, reinterpret_cast<const int4*>(tile_item), heads, tau, tau_min, out, lse, drop);
@@ -469,14 +546,14 @@ int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ld
                           const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
                           const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads, int dh,
                           const float* tau, float tau_min, float* dq, float* dk, float* dv, int lddq, int lddk, int lddv,
-                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st) {
+                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st, int am) {
     if (dh != 6) return SEG3D_EINVAL;
     const int4* ti = reinterpret_cast<const int4*>(tile_item);
-    float* tau_part = static_cast<float*>(workspace);  // n_tiles floats
+    float* tau_part = static_cast<float*>(workspace);  // n_tiles floats (kPerHead: n_tiles x heads)
     if (!attn_small_supported(heads, dh)) return SEG3D_EINVAL;
     if (heads <= 8)
         return run_small_bwd<6, 256>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, heads, tau,
-                                     tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st);
+                                     tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st, am);
     return run_small_bwd<6, 512>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, heads, tau,
-                                 tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st);
+                                 tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st, am);
 }

@@ -12,7 +12,7 @@ bool attn_fused_supported(int heads, int dh);
 int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
                           const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles,
                           const int32_t* chunk_item, int n_chunks, int heads, int dh, const float* tau, float tau_min,
-                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st);
+                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st, int am);
 int attn_fused_fwd_schedule(int n_tiles, int n_chunks, int heads, int dh, bool dropout, int* cap, int* grid, int* walked,
                             int* xb);
 // attention_fused_bwd.hip
@@ -24,19 +24,19 @@ int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ld
                           const int32_t* win_count, const int32_t* tile_item, int n_tiles, const int32_t* chunk_item,
                           int n_chunks, int64_t m, int heads, int dh, const float* tau, float tau_min, float* dq, float* dk,
                           float* dv, int lddq, int lddk, int lddv, float* dtau, void* workspace, const DropoutParams& drop,
-                          hipStream_t st);
+                          hipStream_t st, int am);
 // attention_small.hip
 bool attn_small_supported(int heads, int dh);
 size_t attn_small_blocks(int n_tiles);
 int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
                           const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads,
                           int dh, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-                          hipStream_t st);
+                          hipStream_t st, int am);
 int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
                           const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
                           const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads, int dh,
                           const float* tau, float tau_min, float* dq, float* dk, float* dv, int lddq, int lddk, int lddv,
-                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st);
+                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st, int am);
 
 namespace attn {
 
@@ -45,6 +45,13 @@ using namespace sbf;
 constexpr float kNormEps = 1e-12f;  // F.normalize eps, cosine_msa.py:152-153
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
+
+// Attention modes the kernels are instantiated for (the AM template argument; SEG3D_ATTN_COSINE / _DOT of the header):
+//   kShared   cosine, one tau for all heads (cosine_msa.py:156-160 with non_shared_tau=False): the kernels as they were
+//   kPerHead  cosine, tau[h] per head (non_shared_tau=True): every scale, bound and tau partial belongs to ONE head
+//   kDot      scaled dot product (cosine_msa.py:163-165): no normalisation, scores q.k / sqrt(dh) are unbounded -- always
+//             the running maximum, no tau
+constexpr int kShared = 0, kPerHead = 1, kDot = 2;
 
 // Masking streamed tokens past a window's end INSIDE the score product: the K dimension of the score MFMAs is padded from
 // the stored head width DHS to a multiple of 32, so channel DHS is spare.  The stationary (query) fragment carries 1.0

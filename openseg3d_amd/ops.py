@@ -1728,6 +1728,64 @@ def pos_embed(in_win, window_shape, inv_freq, c):
 
 
 # ------------------------------------------------------------------------------------------ a19-a21 attention
+_TAU_FORMS = ("tau must be a float32 tensor with 1 element (the shared temperature), with `heads` elements of shape "
+              "[1, H, 1, 1] (one per head, non_shared_tau) or None (scaled dot-product attention, cosine=False)")
+
+
+def _attn_tau_check(tau, heads, cosine=None):
+    """The three forms of the attention temperature (cosine_msa.py:413-432); ``cosine``: the layer's own option when the
+    caller has one -- a tau together with cosine=False is refused."""
+    if cosine is False and tau is not None:
+        raise _lib.Seg3dError(f"window attention: a tau was given together with dot-product mode; {_TAU_FORMS}")
+    if tau is None:
+        if cosine:
+            raise _lib.Seg3dError(f"window attention: cosine mode needs a tau; {_TAU_FORMS}")
+        return
+    if not torch.is_tensor(tau) or tau.dtype != torch.float32 or tau.numel() not in (1, int(heads)):
+        got = tuple(tau.shape) if torch.is_tensor(tau) else type(tau).__name__
+        raise _lib.Seg3dError(f"window attention: tau {got} on {heads} heads; {_TAU_FORMS}")
+
+
+def _attn_fwd_call(q, k, v, ldq, ldk, ldv, wi, m, heads, dh, tau, tau_min, drop_p, drop_seed, out, lse):
+    """One tau: seg3d_window_attn_fwd as ever; `heads` values or none: the _modes entry (per-head tau / dot product)."""
+    if tau is not None and tau.numel() == 1:
+        _lib.call("seg3d_window_attn_fwd", q, k, v, ldq, ldk, ldv,
+                  _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count), _ptr(wi.win_tile0), _ptr(wi.tile_item),
+                  int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m, int(wi.n_windows), heads, dh,
+                  _ptr(tau.reshape(-1)), float(tau_min), float(drop_p), int(drop_seed), _ptr(out), _ptr(lse), None, 0,
+                  _stream())  # (no workspace: seg3d_window_attn_workspace_bytes sizes the backward's)
+        return
+    mode, tau_f = (_lib.ATTN_DOT, None) if tau is None else (_lib.ATTN_COSINE, _f32c(tau.reshape(-1)))
+    _lib.call("seg3d_window_attn_fwd_modes", q, k, v, ldq, ldk, ldv, _ptr(wi.tok), _ptr(wi.win_start),
+              _ptr(wi.win_count), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m,
+              int(wi.n_windows), heads, dh, mode, None if tau_f is None else _ptr(tau_f), 0 if tau_f is None else tau_f.numel(),
+              float(tau_min), float(drop_p), int(drop_seed), _ptr(out), _ptr(lse), None, 0, _stream())
+
+
+def _attn_bwd_call(q, k, v, ldq, ldk, ldv, out, dout, lse, wi, m, heads, dh, tau, tau_min, drop_p, drop_seed, dq, dk, dv,
+                   lddq, lddk, lddv, dev):
+    """-> dtau shaped like tau (None in dot mode); written, not accumulated, by the kernels."""
+    if tau is not None and tau.numel() == 1:
+        dtau = torch.empty((1,), dtype=torch.float32, device=dev)
+        ws = _workspace(_lib.query("seg3d_window_attn_workspace_bytes", m, int(wi.n_tiles), heads, dh), dev)
+        _lib.call("seg3d_window_attn_bwd", q, k, v, ldq, ldk, ldv,
+                  _ptr(out), _ptr(dout), _ptr(lse), _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count),
+                  _ptr(wi.win_tile0), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m,
+                  int(wi.n_windows), heads, dh, _ptr(tau.reshape(-1)), float(tau_min), float(drop_p),
+                  int(drop_seed), dq, dk, dv, lddq, lddk, lddv, _ptr(dtau), _ptr(ws), ws.numel(), _stream())
+        return dtau.reshape(tau.shape)
+    mode, tau_f = (_lib.ATTN_DOT, None) if tau is None else (_lib.ATTN_COSINE, _f32c(tau.reshape(-1)))
+    n_tau = 0 if tau_f is None else tau_f.numel()
+    dtau = None if tau_f is None else torch.empty((n_tau,), dtype=torch.float32, device=dev)
+    ws = _workspace(_lib.query("seg3d_window_attn_workspace_bytes_modes", m, int(wi.n_tiles), heads, dh, mode, n_tau), dev)
+    _lib.call("seg3d_window_attn_bwd_modes", q, k, v, ldq, ldk, ldv, _ptr(out), _ptr(dout), _ptr(lse), _ptr(wi.tok),
+              _ptr(wi.win_start), _ptr(wi.win_count), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item),
+              int(wi.n_qgroups), m, int(wi.n_windows), heads, dh, mode, None if tau_f is None else _ptr(tau_f), n_tau,
+              float(tau_min), float(drop_p), int(drop_seed), dq, dk, dv, lddq, lddk, lddv,
+              None if dtau is None else _ptr(dtau), _ptr(ws), ws.numel(), _stream())
+    return None if dtau is None else dtau.reshape(tau.shape)
+
+
 class _WindowAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, tau, tau_min, heads, wi):
@@ -1736,11 +1794,8 @@ class _WindowAttnFn(torch.autograd.Function):
         dev = v.device
         out = torch.empty((m, c), dtype=torch.float32, device=dev)
         lse = torch.empty((m, heads), dtype=torch.float32, device=dev)
-        tau_f = tau.reshape(-1)
-        _lib.call("seg3d_window_attn_fwd", _ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0),
-                  _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count), _ptr(wi.win_tile0), _ptr(wi.tile_item),
-                  int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m, int(wi.n_windows), heads, dh,
-                  _ptr(tau_f), float(tau_min), 0.0, 0, _ptr(out), _ptr(lse), None, 0, _stream())  # (the forward needs no workspace)
+        _attn_fwd_call(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), wi, m, heads, dh, tau, tau_min,
+                       0.0, 0, out, lse)
         ctx.save_for_backward(q, k, v, tau, out, lse)
         ctx.wi, ctx.heads, ctx.tau_min = wi, heads, tau_min
         return out
@@ -1753,14 +1808,9 @@ class _WindowAttnFn(torch.autograd.Function):
         dev = v.device
         dout = _f32c(dout)
         dq, dk, dv = (torch.empty((m, c), dtype=torch.float32, device=dev) for _ in range(3))
-        dtau = torch.empty((1,), dtype=torch.float32, device=dev)  # written (not accumulated) by the kernels
-        ws = _workspace(_lib.query("seg3d_window_attn_workspace_bytes", m, int(wi.n_tiles), heads, c // heads), dev)
-        _lib.call("seg3d_window_attn_bwd", _ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0),
-                  _ptr(out), _ptr(dout), _ptr(lse), _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count),
-                  _ptr(wi.win_tile0), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m,
-                  int(wi.n_windows), heads, c // heads, _ptr(tau.reshape(-1)), float(ctx.tau_min), 0.0, 0, _ptr(dq), _ptr(dk),
-                  _ptr(dv), c, c, c, _ptr(dtau), _ptr(ws), ws.numel(), _stream())
-        return dq, dk, dv, dtau.reshape(tau.shape), None, None, None
+        dtau = _attn_bwd_call(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), out, dout, lse, wi, m, heads,
+                              c // heads, tau, ctx.tau_min, 0.0, 0, _ptr(dq), _ptr(dk), _ptr(dv), c, c, c, dev)
+        return dq, dk, dv, dtau, None, None, None
 
 
 class _WindowAttnPackedFn(torch.autograd.Function):
@@ -1777,11 +1827,7 @@ class _WindowAttnPackedFn(torch.autograd.Function):
         lse = torch.empty((m, heads), dtype=torch.float32, device=dev)
         ctx.drop_p, ctx.drop_seed = drop_p, drop_seed
         kp = ctypes.c_void_p(qk.data_ptr() + 4 * c)
-        _lib.call("seg3d_window_attn_fwd", _ptr(qk), kp, _ptr(v), 2 * c, 2 * c, c,
-                  _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count), _ptr(wi.win_tile0), _ptr(wi.tile_item),
-                  int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m, int(wi.n_windows), heads, dh,
-                  _ptr(tau.reshape(-1)), float(tau_min), float(drop_p), int(drop_seed), _ptr(out), _ptr(lse), None, 0,
-                  _stream())  # (no workspace: seg3d_window_attn_workspace_bytes sizes the backward's)
+        _attn_fwd_call(_ptr(qk), kp, _ptr(v), 2 * c, 2 * c, c, wi, m, heads, dh, tau, tau_min, drop_p, drop_seed, out, lse)
         ctx.save_for_backward(qk, v, tau, out, lse)
         ctx.wi, ctx.heads, ctx.tau_min = wi, heads, tau_min
         return out
@@ -1795,21 +1841,20 @@ class _WindowAttnPackedFn(torch.autograd.Function):
         dout = _f32c(dout)
         dqk = torch.empty((m, 2 * c), dtype=torch.float32, device=dev)
         dv = torch.empty((m, c), dtype=torch.float32, device=dev)
-        dtau = torch.empty((1,), dtype=torch.float32, device=dev)  # written (not accumulated) by the kernels
-        ws = _workspace(_lib.query("seg3d_window_attn_workspace_bytes", m, int(wi.n_tiles), heads, c // heads), dev)
         kp = ctypes.c_void_p(qk.data_ptr() + 4 * c)
         dkp = ctypes.c_void_p(dqk.data_ptr() + 4 * c)
-        _lib.call("seg3d_window_attn_bwd", _ptr(qk), kp, _ptr(v), 2 * c, 2 * c, c,
-                  _ptr(out), _ptr(dout), _ptr(lse), _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count),
-                  _ptr(wi.win_tile0), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m,
-                  int(wi.n_windows), heads, c // heads, _ptr(tau.reshape(-1)), float(ctx.tau_min), float(ctx.drop_p),
-                  int(ctx.drop_seed), _ptr(dqk), dkp, _ptr(dv), 2 * c, 2 * c, c, _ptr(dtau), _ptr(ws), ws.numel(), _stream())
-        return dqk, dv, dtau.reshape(tau.shape), None, None, None, None, None
+        dtau = _attn_bwd_call(_ptr(qk), kp, _ptr(v), 2 * c, 2 * c, c, out, dout, lse, wi, m, heads, c // heads, tau,
+                              ctx.tau_min, ctx.drop_p, ctx.drop_seed, _ptr(dqk), dkp, _ptr(dv), 2 * c, 2 * c, c, dev)
+        return dqk, dv, dtau, None, None, None, None, None
 
 
-def window_attention_packed(qk, v, tau, tau_min, heads, wi, drop_p=0.0, drop_seed=0):
+def window_attention_packed(qk, v, tau, tau_min, heads, wi, drop_p=0.0, drop_seed=0, cosine=None):
     """qk: contiguous float32 [m, 2C] (q | k), v: contiguous float32 [m, C].  drop_p / drop_seed: attention-probability
-    dropout of training mode (cosine_msa.py:172-174), mask = f(seed, window, head, query, key)."""
+    dropout of training mode (cosine_msa.py:172-174), mask = f(seed, window, head, query, key).
+    tau: one element (shared), `heads` elements [1, H, 1, 1] (per head; the gradient has that shape) or None (scaled
+    dot-product attention, cosine_msa.py:163-165; no tau gradient).  cosine: the caller's own mode, if it has one (a layer's
+    constructor option): True with no tau and False with a tau are refused."""
+    _attn_tau_check(tau, heads, cosine)
     _need_gpu(qk, v, tau)
     if qk.dtype != torch.float32 or v.dtype != torch.float32 or not qk.is_contiguous() or not v.is_contiguous() \
             or qk.shape[1] != 2 * v.shape[1]:
@@ -1888,8 +1933,10 @@ def attn_in_proj(x, pos, w_in, b_in):
     return _AttnInProjFn.apply(x, pos, w_in, b_in)
 
 
-def window_attention(q, k, v, tau, tau_min, heads, wi):
-    """q, k, v: float32 [m, C] row-strided views (last dim contiguous) of the in-projection output."""
+def window_attention(q, k, v, tau, tau_min, heads, wi, cosine=None):
+    """q, k, v: float32 [m, C] row-strided views (last dim contiguous) of the in-projection output; tau as in
+    window_attention_packed."""
+    _attn_tau_check(tau, heads, cosine)
     _need_gpu(q, k, v, tau)
     for t in (q, k, v):
         if t.dtype != torch.float32 or t.stride(1) != 1:

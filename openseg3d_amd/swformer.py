@@ -128,18 +128,26 @@ class SparseWindowPartitionLayer(nn.Module):
 
 
 class CosineMultiheadAttention(nn.Module):
-    """Parameters of cosine_msa.CosineMultiheadAttention (packed in-proj, out-proj, shared tau); the
-    attention core runs in seg3d_window_attn_fwd/bwd."""
+    """Parameters of cosine_msa.CosineMultiheadAttention (packed in-proj, out-proj, tau); the attention core runs in
+    seg3d_window_attn_fwd / _bwd (shared tau) or seg3d_window_attn_fwd_modes / _bwd_modes.  ``non_shared_tau``: one
+    learnable tau per head, [1, H, 1, 1] (cosine_msa.py:413-432, :156-160); ``cosine=False``: plain scaled dot-product
+    attention (:163-165), no tau parameter -- the reference's keys and shapes in every case."""
 
-    def __init__(self, embed_dim, num_heads, dropout=0.0, tau_min=0.01):
+    def __init__(self, embed_dim, num_heads, dropout=0.0, tau_min=0.01, cosine=True, non_shared_tau=False):
         super().__init__()
         if embed_dim % num_heads:
             raise ValueError("embed_dim must be divisible by num_heads")
         self.embed_dim, self.num_heads, self.tau_min, self.dropout = embed_dim, num_heads, tau_min, dropout
+        self.cosine, self.non_shared_tau = bool(cosine), bool(non_shared_tau)
         self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
         self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
         self.out_proj = nn.Linear(embed_dim, embed_dim)
-        self.tau = nn.Parameter(torch.ones(1, 1, 1))
+        if not self.cosine:
+            self.register_parameter("tau", None)  # (no key in the state dict, as in the reference)
+        elif self.non_shared_tau:
+            self.tau = nn.Parameter(torch.ones(1, num_heads, 1, 1))
+        else:
+            self.tau = nn.Parameter(torch.ones(1, 1, 1))
         nn.init.xavier_uniform_(self.in_proj_weight)  # nn.MultiheadAttention._reset_parameters
         nn.init.constant_(self.out_proj.bias, 0.0)
 
@@ -156,14 +164,17 @@ class CosineMultiheadAttention(nn.Module):
         """x [M, C] flat voxel features, pos [M, C]; q = k = (x + pos) W_qk, v = x W_v (cosine_msa.py:58-63)."""
         qk, v = ops.attn_in_proj(x, pos, self.in_proj_weight, self.in_proj_bias)
         drop_p, drop_seed = self.drop_args(seed)
-        o = ops.window_attention_packed(qk, v, self.tau, self.tau_min, self.num_heads, wi, drop_p, drop_seed)
+        o = ops.window_attention_packed(qk, v, self.tau, self.tau_min, self.num_heads, wi, drop_p, drop_seed,
+                                        cosine=self.cosine)
         return ops.linear(o, self.out_proj.weight, self.out_proj.bias)
 
 
 class WindowAttention(nn.Module):
-    def __init__(self, d_model, nhead, attn_drop, tau_min=0.01):
+    def __init__(self, d_model, nhead, attn_drop, cosine=True, tau_min=0.01, non_shared_tau=False):
         super().__init__()
-        self.self_attn = CosineMultiheadAttention(d_model, nhead, dropout=attn_drop, tau_min=tau_min)
+        # (point_transformer_layer.py:222-231 takes cosine and tau_min; non_shared_tau is handed through for EncoderLayer)
+        self.self_attn = CosineMultiheadAttention(d_model, nhead, dropout=attn_drop, tau_min=tau_min, cosine=cosine,
+                                                  non_shared_tau=non_shared_tau)
 
     def forward(self, feat_2d, pos, wi, seed=0):
         return self.self_attn(feat_2d, pos, wi, seed)
@@ -214,9 +225,11 @@ FUSED_LAYER = os.environ.get("SEG3D_FUSED_LAYER", "1") != "0"
 class EncoderLayer(nn.Module):
     """Post-norm encoder layer: x + DP(LN1(attn(x))), then + DP(LN2(mlp(.))) (point_transformer_layer.py:289-298)."""
 
-    def __init__(self, d_model, nhead, mlp_hidden_dim, drop=0.0, attn_drop=0.1, drop_path_rate=0.0):
+    def __init__(self, d_model, nhead, mlp_hidden_dim, drop=0.0, attn_drop=0.1, drop_path_rate=0.0, cosine=True,
+                 non_shared_tau=False):
         super().__init__()
-        self.win_attn = WindowAttention(d_model, nhead, attn_drop)
+        # cosine / non_shared_tau: the attention's two constructor options (the reference fixes the defaults at this level)
+        self.win_attn = WindowAttention(d_model, nhead, attn_drop, cosine=cosine, non_shared_tau=non_shared_tau)
         self.norm1 = nn.LayerNorm(d_model)
         self.norm2 = nn.LayerNorm(d_model)
         self.mlp = MLP(d_model, mlp_hidden_dim, drop=drop)
@@ -249,13 +262,14 @@ class EncoderLayer(nn.Module):
 
 
 class SWFormerBlock(nn.Module):
-    def __init__(self, d_model, nhead, depth=4, mlp_ratio=2.0, attn_drop=0.1, drop=0.0, drop_path=0.0):
+    def __init__(self, d_model, nhead, depth=4, mlp_ratio=2.0, attn_drop=0.1, drop=0.0, drop_path=0.0, cosine=True,
+                 non_shared_tau=False):
         super().__init__()
         self.depth = depth
         rates = drop_path if isinstance(drop_path, (list, tuple)) else [drop_path] * depth
         self.layers = nn.ModuleList(
             EncoderLayer(d_model, nhead, int(d_model * mlp_ratio), drop=drop, attn_drop=attn_drop,
-                         drop_path_rate=rates[i]) for i in range(depth))
+                         drop_path_rate=rates[i], cosine=cosine, non_shared_tau=non_shared_tau) for i in range(depth))
         self._keep = None  # [2 * depth, 1] keep probabilities on the device (built on first use)
 
     def forward(self, voxel_info):
