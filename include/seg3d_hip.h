@@ -62,8 +62,10 @@ int seg3d_grid_size(const float* voxel_size, const float* range, int32_t* grid_x
  *          seg3d/datasets/waymo_dataset.py:339-365.
  * Hard voxelisation with first-seen voxel order, on device, for a whole collated batch:
  * c_j = floor((p_j - lo_j) / vs_j) with an IEEE subtract and true divide in the dtype of
- * `points`; a point is rejected (id -1) if any c_j is outside [0, grid_j).
- *   points      [n, row_stride] row-major; xyz at columns xyz_col..xyz_col+2;
+ * `points`; a point is rejected (id -1) if any c_j is outside [0, grid_j).  A point with a
+ * non-finite coordinate (NaN, +Inf, -Inf) is rejected in the same way, like the reference's
+ * out-of-range points.
+ *   points     [n, row_stride] row-major; xyz at columns xyz_col..xyz_col+2;
  *               batch id (stored as a float, as the reference collates it) at batch_col, or
  *               batch_col < 0 for a single sample (batch id 0)
  *   voxel_size, range: host float[3], float[6]  (float32 constants, widened for the f64 entry)
@@ -390,6 +392,7 @@ int seg3d_linear_fwd_mul(const float* x, int64_t m, const void* w_packed, const 
  *   win_id   batch_win_inds            in_win [m,3]  coors_in_win as (z,y,x)
  *   rank     in-window rank (ascending voxel row)    level  batching level, -1 if no range matches
  *   slot     flat2window index = compact_window_in_level * max_tokens + rank; -1 if rank >= max_tokens
+ *            or level is -1 (such a window takes no compact index in any level)
  *   tok      voxel rows grouped by window (ascending window id, ascending row inside)
  *   win_start/win_count [<= min(m, canvas)]  CSR of the non-empty windows into tok
  *   win_tile0 [<= min(m, canvas)]  first 32-token tile of each window in the 32-padded token space

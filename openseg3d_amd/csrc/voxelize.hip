@@ -44,7 +44,8 @@ __global__ __launch_bounds__(kThreads) void vox_insert(const T* __restrict__ pts
         for (int j = 0; j < 3; ++j) {
             // voxel_generator.py:139 -- subtract and TRUE divide in the point dtype, then floor
             T v = floor_t((row[p.xyz_col + j] - c.lo[j]) / c.vs[j]);
-            if (v < (T)0 || v >= (T)p.grid[j]) valid = false;
+            // !(v >= 0), not v < 0: a NaN fails every comparison and is rejected, as in the host entry below
+            if (!(v >= (T)0) || v >= (T)p.grid[j]) valid = false;
             cc[j] = (int32_t)v;
         }
         if (valid) {

@@ -61,9 +61,10 @@ __global__ __launch_bounds__(kThreads) void win_level_flags(const uint32_t* __re
     const int64_t w = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (w >= n_canvas) return;
     const uint32_t n = count[w];
-    // windows whose count matches no range still take a compact slot (lane 3 + marker in level -1)
+    // a window whose count matches no range (level -1) is in no lane: make_continuous_inds counts a level's own
+    // windows only, and its voxels get slot -1
     const int l = n ? level_of(n, lv) : -2;
-    flags[w] = make_uint4(l == 0, l == 1, l == 2, (l == 3) || (l == -1));
+    flags[w] = make_uint4(l == 0, l == 1, l == 2, l == 3);
 }
 
 __global__ __launch_bounds__(kThreads) void win_per_voxel(const int32_t* __restrict__ win_id, const int32_t* __restrict__ rank,

@@ -89,7 +89,8 @@ static inline int32_t omap_get(const omap *m, int64_t k) {
             point_voxel_ids[i] = -1;                                                  \
             for (int j = 0; j < 3; ++j) {                                             \
                 T c = FLOOR((points[i * stride + j] - coors_range[j]) / voxel_size[j]); \
-                if (c < 0 || c >= (T)grid[j]) { failed = 1; break; }                  \
+                /* the reference tests c < 0 || c >= grid and casts a NaN; rejected here */ \
+                if (!(c >= 0) || c >= (T)grid[j]) { failed = 1; break; }              \
                 coor[2 - j] = (int32_t)c;                                             \
             }                                                                         \
             if (failed) continue;                                                     \
