@@ -656,34 +656,29 @@ FwdSchedule fwd_schedule(int n_tiles, int n_chunks, int heads, bool dropout) {
     return s;
 }
 
+// The shared-tau kernel keeps its own name, attn_fused_fwd (profiles and resource tables know it by that); the other two
+// modes are attn_fused_fwd_modes.  Same parameters: one launch line takes either.
+template <int DH, bool DROPOUT, int AM>
+constexpr auto fwd_kernel() {
+    if constexpr (AM == kShared) return &attn_fused_fwd<DH, DROPOUT>;
+    else return &attn_fused_fwd_modes<DH, DROPOUT, AM>;
+}
+
 template <int DH>
-int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-           const int32_t* win_start, const int32_t* win_count, const int4* tile_item, int n_tiles, const int4* chunk_item,
-           int n_chunks, int heads, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-           hipStream_t st, int am = kShared) {
+int launch(const AttnArgs& a, float* out, float* lse) {
     using C = Cfg<DH>;
-    const int4* items = C::kNarrow ? tile_item : chunk_item;
-    const FwdSchedule s = fwd_schedule<DH>(n_tiles, n_chunks, heads, drop.threshold != 0);
-    const int n_items = s.n_items, xg = s.xg, xb = s.xb;
-    const dim3 grid((unsigned)s.grid);
-#define SEG3D_FWD_MODE(DROP, AM)                                                                                                   \
-    hipLaunchKernelGGL((attn_fused_fwd_modes<DH, DROP, AM>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, tok, win_start,       \
-                       win_count, items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb)
-    if (am == kPerHead) {
-        if (drop.threshold) SEG3D_FWD_MODE(true, kPerHead);
-        else SEG3D_FWD_MODE(false, kPerHead);
-    } else if (am == kDot) {
-        if (drop.threshold) SEG3D_FWD_MODE(true, kDot);
-        else SEG3D_FWD_MODE(false, kDot);
-    } else if (drop.threshold)
-        hipLaunchKernelGGL((attn_fused_fwd<DH, true>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, tok, win_start, win_count,
-                           items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb);
-    else
-        hipLaunchKernelGGL((attn_fused_fwd<DH, false>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, tok, win_start, win_count,
-                           items, n_items, heads, tau, tau_min, out, lse, drop, xg, xb);
-#undef SEG3D_FWD_MODE
-    SEG3D_CHECK_LAUNCH();
-    return SEG3D_OK;
+    const int4* items = C::kNarrow ? a.tile_item : a.chunk_item;
+    const FwdSchedule s = fwd_schedule<DH>(a.n_tiles, a.n_chunks, a.heads, a.drop.threshold != 0);
+    auto run = [&](auto kernel) -> int {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)s.grid), dim3(256), 0, a.st, a.q, a.k, a.v, a.ldq, a.ldk, a.ldv, a.tok,
+                           a.win_start, a.win_count, items, s.n_items, a.heads, a.tau, a.tau_min, out, lse, a.drop, s.xg, s.xb);
+        SEG3D_CHECK_LAUNCH();
+        return SEG3D_OK;
+    };
+    return for_attn_mode(a.am, [&](auto mode) -> int {
+        constexpr int AM = decltype(mode)::value;
+        return a.drop.threshold ? run(fwd_kernel<DH, true, AM>()) : run(fwd_kernel<DH, false, AM>());
+    });
 }
 
 template <int DH>
@@ -705,18 +700,12 @@ bool attn_fused_supported(int heads, int dh) {
     return dh == 24 || dh == 48;
 }
 
-int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles,
-                          const int32_t* chunk_item, int n_chunks, int heads, int dh, const float* tau, float tau_min,
-                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st, int am) {
-    const DropoutParams drop = make_dropout(dropout_p, seed);
-    const int4* ti = reinterpret_cast<const int4*>(tile_item);
-    const int4* ci = reinterpret_cast<const int4*>(chunk_item);
-    switch (dh) {
-        case 6: return launch<6>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
-        case 12: return launch<12>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
-        case 24: return launch<24>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
-        case 48: return launch<48>(q, k, v, ldq, ldk, ldv, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, tau, tau_min, out, lse, drop, st, am);
+int attn_fused_fwd_launch(const AttnArgs& a, float* out, float* lse) {
+    switch (a.dh) {
+        case 6: return launch<6>(a, out, lse);
+        case 12: return launch<12>(a, out, lse);
+        case 24: return launch<24>(a, out, lse);
+        case 48: return launch<48>(a, out, lse);
         default: return SEG3D_EINVAL;
     }
 }

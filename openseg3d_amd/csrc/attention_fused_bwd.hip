@@ -847,48 +847,41 @@ __global__ __launch_bounds__(1024) void tau_reduce_fused(const float* __restrict
     }
 }
 
+size_t tau_part_bytes(int n_tiles, int n_chunks, int heads, int dh) {
+    return align_up(attn_fused_bwd_blocks(n_tiles, n_chunks, heads, dh) * 4 * sizeof(float), 256);
+}
+
+// One backward in every attention mode: pass Q (tau partials, delta) -> the partials' sum in a fixed order (kShared: one value,
+// kPerHead: one per head, kDot: no tau) -> pass KV.  The workspace: one tau partial per wave of pass Q, then delta.
 template <int DH>
-int launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out, const float* dout,
-           const float* lse, const int32_t* tok, const int32_t* win_start, const int32_t* win_count, const int4* tile_item,
-           int n_tiles, const int4* chunk_item, int n_chunks, int heads, const float* tau, float tau_min, float* dq, float* dk,
-           float* dv, int lddq, int lddk, int lddv, float* dtau, float* tau_part, float* delta_buf, const DropoutParams& drop,
-           hipStream_t st, int am) {
+int launch(const AttnBwdArgs& a) {
     using C = Cfg<DH>;
-    const int4* items = C::kNarrow ? tile_item : chunk_item;
-    const int n_items = C::kNarrow ? n_tiles : n_chunks;
+    const int4* items = C::kNarrow ? a.tile_item : a.chunk_item;
+    const int n_items = C::kNarrow ? a.n_tiles : a.n_chunks;
     const int xb = xcd_block_items(C::kNarrow, n_items);
-    const dim3 grid((unsigned)attn_fused_bwd_blocks(n_tiles, n_chunks, heads, DH));
-#define SEG3D_BWD_MODE(PASS, AM, PART)                                                                                            \
-    hipLaunchKernelGGL((attn_fused_bwd<DH, PASS + 2 * AM>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, out, dout, lse, tok, \
-                       win_start, win_count, items, n_items, heads, tau, tau_min, dq, lddq, dk, lddk, dv, lddv, PART, delta_buf,  \
-                       drop, xb)
-    if (am == kPerHead) {
-        SEG3D_BWD_MODE(0, kPerHead, tau_part);
-        SEG3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(tau_reduce_heads, dim3((unsigned)heads), dim3(256), 0, st, tau_part, (int)grid.x, heads / C::HG,
-                           C::kNarrow ? 1 : 0, dtau);
-        SEG3D_CHECK_LAUNCH();
-        SEG3D_BWD_MODE(1, kPerHead, nullptr);
+    const dim3 grid((unsigned)attn_fused_bwd_blocks(a.n_tiles, a.n_chunks, a.heads, DH));
+    float* tau_part = static_cast<float*>(a.workspace);
+    float* delta_buf = reinterpret_cast<float*>(static_cast<char*>(a.workspace) + tau_part_bytes(a.n_tiles, a.n_chunks, a.heads, DH));
+    auto pass = [&](auto kernel, float* part) -> int {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, a.st, a.q, a.k, a.v, a.ldq, a.ldk, a.ldv, a.out, a.dout, a.lse, a.tok,
+                           a.win_start, a.win_count, items, n_items, a.heads, a.tau, a.tau_min, a.dq, a.lddq, a.dk, a.lddk, a.dv,
+                           a.lddv, part, delta_buf, a.drop, xb);
         SEG3D_CHECK_LAUNCH();
         return SEG3D_OK;
-    }
-    if (am == kDot) {
-        SEG3D_BWD_MODE(0, kDot, nullptr);
-        SEG3D_CHECK_LAUNCH();
-        SEG3D_BWD_MODE(1, kDot, nullptr);
-        SEG3D_CHECK_LAUNCH();
-        return SEG3D_OK;
-    }
-#undef SEG3D_BWD_MODE
-    hipLaunchKernelGGL((attn_fused_bwd<DH, 0>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start,
-                       win_count, items, n_items, heads, tau, tau_min, dq, lddq, dk, lddk, dv, lddv, tau_part, delta_buf, drop, xb);
-    SEG3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(tau_reduce_fused, dim3(1), dim3(1024), 0, st, tau_part, (int)(grid.x * 4), dtau);
-    SEG3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL((attn_fused_bwd<DH, 1>), grid, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start,
-                       win_count, items, n_items, heads, tau, tau_min, dq, lddq, dk, lddk, dv, lddv, nullptr, delta_buf, drop, xb);
-    SEG3D_CHECK_LAUNCH();
-    return SEG3D_OK;
+    };
+    return for_attn_mode(a.am, [&](auto mode) -> int {
+        constexpr int AM = decltype(mode)::value;
+        if (const int rc = pass(&attn_fused_bwd<DH, 0 + 2 * AM>, AM == kDot ? nullptr : tau_part)) return rc;
+        if (AM == kShared) {
+            hipLaunchKernelGGL(tau_reduce_fused, dim3(1), dim3(1024), 0, a.st, tau_part, (int)(grid.x * 4), a.dtau);
+            SEG3D_CHECK_LAUNCH();
+        } else if (AM == kPerHead) {
+            hipLaunchKernelGGL(tau_reduce_heads, dim3((unsigned)a.heads), dim3(256), 0, a.st, tau_part, (int)grid.x,
+                               a.heads / C::HG, C::kNarrow ? 1 : 0, a.dtau);
+            SEG3D_CHECK_LAUNCH();
+        }
+        return pass(&attn_fused_bwd<DH, 1 + 2 * AM>, nullptr);
+    });
 }
 
 }  // namespace
@@ -908,36 +901,17 @@ size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh) {
                     : bwd_blocks(n_chunks, heads, xcd_block_items(false, n_chunks));
 }
 
-static size_t tau_part_bytes(int n_tiles, int n_chunks, int heads, int dh) {
-    return align_up(attn_fused_bwd_blocks(n_tiles, n_chunks, heads, dh) * 4 * sizeof(float), 256);
-}
-
 // one dtau partial per wave of pass Q + delta = <dO, O> per (token, head), handed from pass Q to pass KV
 size_t attn_fused_bwd_workspace_bytes(int64_t m, int n_tiles, int n_chunks, int heads, int dh) {
     return tau_part_bytes(n_tiles, n_chunks, heads, dh) + align_up((size_t)m * heads * sizeof(float), 256) + 256;
 }
 
-int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
-                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
-                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, const int32_t* chunk_item,
-                          int n_chunks, int64_t m, int heads, int dh, const float* tau, float tau_min, float* dq, float* dk,
-                          float* dv, int lddq, int lddk, int lddv, float* dtau, void* workspace, const DropoutParams& drop,
-                          hipStream_t st, int am) {
-    (void)m;
-    const int4* ti = reinterpret_cast<const int4*>(tile_item);
-    const int4* ci = reinterpret_cast<const int4*>(chunk_item);
-    float* tau_part = static_cast<float*>(workspace);
-    float* delta_buf = reinterpret_cast<float*>(static_cast<char*>(workspace) + tau_part_bytes(n_tiles, n_chunks, heads, dh));
-#define SEG3D_FB(D)                                                                                                        \
-    case D:                                                                                                                \
-        return launch<D>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, ci, n_chunks, heads, \
-                         tau, tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, delta_buf, drop, st, am)
-    switch (dh) {
-        SEG3D_FB(6);
-        SEG3D_FB(12);
-        SEG3D_FB(24);
-        SEG3D_FB(48);
+int attn_fused_bwd_launch(const AttnBwdArgs& a) {
+    switch (a.dh) {
+        case 6: return launch<6>(a);
+        case 12: return launch<12>(a);
+        case 24: return launch<24>(a);
+        case 48: return launch<48>(a);
         default: return SEG3D_EINVAL;
     }
-#undef SEG3D_FB
 }

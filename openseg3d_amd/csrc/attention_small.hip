@@ -457,81 +457,53 @@ __global__ __launch_bounds__(1024) void tau_reduce_small(const float* __restrict
     }
 }
 
+// One backward in every attention mode: pass Q's tau partials -> their sum in a fixed order (kShared: one value, kPerHead: one
+// per head, kDot: no tau) -> pass KV.
 template <int DH, int THREADS>
-int run_small_bwd(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
-                  const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
-                  const int32_t* win_count, const int4* tile_item, int n_tiles, int heads, const float* tau, float tau_min,
-                  float* dq, float* dk, float* dv, int lddq, int lddk, int lddv, float* dtau, float* tau_part,
-                  const DropoutParams& drop, hipStream_t st, int am) {
-    const size_t smem_q = (size_t)2 * kTile * heads * DH * sizeof(float);
-    if (am != kShared) {
-        const dim3 grid((unsigned)attn_small_blocks(n_tiles)), block(32 * heads);
-        const size_t smem_kv2 = smem_q + (size_t)kTile * heads * 2 * sizeof(float);
-#define SEG3D_SMALL_BWD_MODE(AM)                                                                                                   \
-    hipLaunchKernelGGL((attn_small_bwd_q<DH, THREADS + AM>), grid, block, smem_q, st, q, k, v, ldq, ldk, ldv, out, dout, lse,   \
-                       tok, win_start, win_count, tile_item, heads, tau, tau_min, dq, lddq, tau_part, drop);                        \
-    SEG3D_CHECK_LAUNCH();                                                                                                          \
-    if (AM == kPerHead) {                                                                                                          \
-        hipLaunchKernelGGL(tau_reduce_small_heads, dim3((unsigned)heads), dim3(256), 0, st, tau_part, n_tiles, heads, dtau);        \
-        SEG3D_CHECK_LAUNCH();                                                                                                      \
-    }                                                                                                                              \
-    hipLaunchKernelGGL((attn_small_bwd_kv<DH, THREADS + AM>), grid, block, smem_kv2, st, q, k, v, ldq, ldk, ldv, out, dout,     \
-                       lse, tok, win_start, win_count, tile_item, heads, tau, tau_min, dk, lddk, dv, lddv, drop);                   \
-    SEG3D_CHECK_LAUNCH()
-        if (am == kPerHead) {
-            SEG3D_SMALL_BWD_MODE(kPerHead);
-        } else {
-            SEG3D_SMALL_BWD_MODE(kDot);
+int run_small_bwd(const AttnBwdArgs& a) {
+    const dim3 grid((unsigned)attn_small_blocks(a.n_tiles)), block(32 * a.heads);
+    const size_t smem_q = (size_t)2 * kTile * a.heads * DH * sizeof(float);
+    const size_t smem_kv = smem_q + (size_t)kTile * a.heads * 2 * sizeof(float);
+    float* tau_part = static_cast<float*>(a.workspace);  // n_tiles floats (kPerHead: n_tiles x heads)
+    auto passes = [&](auto mode) -> int {
+        constexpr int AM = decltype(mode)::value;
+        hipLaunchKernelGGL((attn_small_bwd_q<DH, THREADS + AM>), grid, block, smem_q, a.st, a.q, a.k, a.v, a.ldq, a.ldk, a.ldv,
+                           a.out, a.dout, a.lse, a.tok, a.win_start, a.win_count, a.tile_item, a.heads, a.tau, a.tau_min, a.dq,
+                           a.lddq, tau_part, a.drop);
+        SEG3D_CHECK_LAUNCH();
+        if (AM == kShared) {
+            hipLaunchKernelGGL(tau_reduce_small, dim3(1), dim3(1024), 0, a.st, tau_part, a.n_tiles, a.dtau);
+            SEG3D_CHECK_LAUNCH();
+        } else if (AM == kPerHead) {
+            hipLaunchKernelGGL(tau_reduce_small_heads, dim3((unsigned)a.heads), dim3(256), 0, a.st, tau_part, a.n_tiles, a.heads,
+                               a.dtau);
+            SEG3D_CHECK_LAUNCH();
         }
-#undef SEG3D_SMALL_BWD_MODE
+        hipLaunchKernelGGL((attn_small_bwd_kv<DH, THREADS + AM>), grid, block, smem_kv, a.st, a.q, a.k, a.v, a.ldq, a.ldk, a.ldv,
+                           a.out, a.dout, a.lse, a.tok, a.win_start, a.win_count, a.tile_item, a.heads, a.tau, a.tau_min, a.dk,
+                           a.lddk, a.dv, a.lddv, a.drop);
+        SEG3D_CHECK_LAUNCH();
         return SEG3D_OK;
-    }
-    hipLaunchKernelGGL((attn_small_bwd_q<DH, THREADS>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem_q, st, q, k, v, ldq, ldk, ldv,
-                       out, dout, lse, tok, win_start, win_count, tile_item, heads, tau, tau_min, dq, lddq, tau_part, drop);
-    SEG3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(tau_reduce_small, dim3(1), dim3(1024), 0, st, tau_part, n_tiles, dtau);
-    SEG3D_CHECK_LAUNCH();
-    const size_t smem_kv = smem_q + (size_t)kTile * heads * 2 * sizeof(float);
-    hipLaunchKernelGGL((attn_small_bwd_kv<DH, THREADS>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem_kv, st, q, k, v, ldq, ldk, ldv,
-                       out, dout, lse, tok, win_start, win_count, tile_item, heads, tau, tau_min, dk, lddk, dv, lddv, drop);
-    SEG3D_CHECK_LAUNCH();
-    return SEG3D_OK;
+    };
+    return for_attn_mode(a.am, passes);
 }
 
 }  // namespace
 
-int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads,
-                          int dh, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-                          hipStream_t st, int am) {
-    if (dh != 6) return SEG3D_EINVAL;
-    const size_t smem = (size_t)2 * kTile * heads * 6 * sizeof(float);
-    if (!attn_small_supported(heads, dh)) return SEG3D_EINVAL;
-    if (am != kShared) {
-        const dim3 grid((unsigned)attn_small_blocks(n_tiles)), block(32 * heads);
-        const int4* ti = reinterpret_cast<const int4*>(tile_item);
-#define SEG3D_SMALL_FWD_MODE(T, AM)                                                                                           \
-    hipLaunchKernelGGL((attn_small_fwd<6, T + AM>), grid, block, smem, st, q, k, v, ldq, ldk, ldv, tok, win_start, win_count, \
-                       ti, heads, tau, tau_min, out, lse, drop)
-        if (am == kPerHead) {
-            if (heads <= 8) SEG3D_SMALL_FWD_MODE(256, kPerHead);
-            else SEG3D_SMALL_FWD_MODE(512, kPerHead);
-        } else {
-            if (heads <= 8) SEG3D_SMALL_FWD_MODE(256, kDot);
-            else SEG3D_SMALL_FWD_MODE(512, kDot);
-        }
-#undef SEG3D_SMALL_FWD_MODE
+int attn_small_fwd_launch(const AttnArgs& a, float* out, float* lse) {
+    if (!attn_small_supported(a.heads, a.dh)) return SEG3D_EINVAL;
+    const size_t smem = (size_t)2 * kTile * a.heads * 6 * sizeof(float);
+    auto run = [&](auto kernel) -> int {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)attn_small_blocks(a.n_tiles)), dim3(32 * a.heads), smem, a.st, a.q, a.k, a.v,
+                           a.ldq, a.ldk, a.ldv, a.tok, a.win_start, a.win_count, a.tile_item, a.heads, a.tau, a.tau_min, out, lse,
+                           a.drop);
         SEG3D_CHECK_LAUNCH();
         return SEG3D_OK;
-    }
-    if (heads <= 8)
-        hipLaunchKernelGGL((attn_small_fwd<6, 256>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem, st, q, k, v, ldq, ldk, ldv, tok,
-                           win_start, win_count, reinterpret_cast<const int4*>(tile_item), heads, tau, tau_min, out, lse, drop);
-    else
-        hipLaunchKernelGGL((attn_small_fwd<6, 512>), dim3((unsigned)attn_small_blocks(n_tiles)), dim3(32 * heads), smem, st, q, k, v, ldq, ldk, ldv, tok,
-                           win_start, win_count, reinterpret_cast<const int4*>(tile_item), heads, tau, tau_min, out, lse, drop);
-    SEG3D_CHECK_LAUNCH();
-    return SEG3D_OK;
+    };
+    return for_attn_mode(a.am, [&](auto mode) -> int {
+        constexpr int AM = decltype(mode)::value;
+        return a.heads <= 8 ? run(&attn_small_fwd<6, 256 + AM>) : run(&attn_small_fwd<6, 512 + AM>);
+    });
 }
 
 // one workgroup per (window, 32-token tile) item in the forward and in both backward passes (no persistent loop); also read by
@@ -542,18 +514,7 @@ size_t attn_small_blocks(int n_tiles) { return n_tiles > 0 ? (size_t)n_tiles : 0
 // 512-thread build; head counts in between stay refused, as they always were)
 bool attn_small_supported(int heads, int dh) { return dh == 6 && heads >= 1 && (heads <= 8 || heads == kMaxHeads); }
 
-int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
-                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
-                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads, int dh,
-                          const float* tau, float tau_min, float* dq, float* dk, float* dv, int lddq, int lddk, int lddv,
-                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st, int am) {
-    if (dh != 6) return SEG3D_EINVAL;
-    const int4* ti = reinterpret_cast<const int4*>(tile_item);
-    float* tau_part = static_cast<float*>(workspace);  // n_tiles floats (kPerHead: n_tiles x heads)
-    if (!attn_small_supported(heads, dh)) return SEG3D_EINVAL;
-    if (heads <= 8)
-        return run_small_bwd<6, 256>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, heads, tau,
-                                     tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st, am);
-    return run_small_bwd<6, 512>(q, k, v, ldq, ldk, ldv, out, dout, lse, tok, win_start, win_count, ti, n_tiles, heads, tau,
-                                 tau_min, dq, dk, dv, lddq, lddk, lddv, dtau, tau_part, drop, st, am);
+int attn_small_bwd_launch(const AttnBwdArgs& a) {
+    if (!attn_small_supported(a.heads, a.dh)) return SEG3D_EINVAL;
+    return a.heads <= 8 ? run_small_bwd<6, 256>(a) : run_small_bwd<6, 512>(a);
 }

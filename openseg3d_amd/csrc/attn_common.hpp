@@ -5,38 +5,50 @@
 
 #include "attn_dropout.hpp"  // after the HIP runtime's header: DropoutParams
 
+// One window-attention call by name: what an entry of attention.hip hands to a launcher and the launcher hands on to
+// launch<DH> / run_small_bwd, which unpack it only at the hipLaunchKernelGGL line.  Strides in floats, n_chunks <= n_tiles.
+struct AttnArgs {
+    const float *q, *k, *v;                      // operands: rows of heads x dh floats
+    int ldq, ldk, ldv;
+    const int32_t *tok, *win_start, *win_count;  // the window index (seg3d_window_partition)
+    const int4* tile_item;                       // (window, 32-token tile) items, as the kernels read them
+    int n_tiles;
+    const int4* chunk_item;                      // (window, 128-token chunk) items: the header's qg_item
+    int n_chunks;
+    int64_t m;
+    int heads, dh;
+    const float* tau;                            // 1 (kShared) / heads (kPerHead) values, null in kDot
+    float tau_min;
+    int am;                                      // attn::kShared / kPerHead / kDot (below)
+    DropoutParams drop;
+    hipStream_t st;
+};
+
+struct AttnBwdArgs : AttnArgs {
+    const float *out, *dout, *lse;
+    float *dq, *dk, *dv;
+    int lddq, lddk, lddv;
+    float* dtau;      // 1 / heads values, written; null in kDot
+    void* workspace;  // attn_fused_bwd_workspace_bytes / attn_small_blocks x (tau values) floats
+};
+
 // The launchers and queries behind the entry points of attention.hip, declared once for the file that defines them and
-// for their callers.  n_chunks <= n_tiles; workspace sizes in bytes, block counts in workgroups.
+// for their callers.  Workspace sizes in bytes, block counts in workgroups.
 // attention_fused.hip
 bool attn_fused_supported(int heads, int dh);
-int attn_fused_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles,
-                          const int32_t* chunk_item, int n_chunks, int heads, int dh, const float* tau, float tau_min,
-                          float* out, float* lse, float dropout_p, uint64_t seed, hipStream_t st, int am);
+int attn_fused_fwd_launch(const AttnArgs& a, float* out, float* lse);
 int attn_fused_fwd_schedule(int n_tiles, int n_chunks, int heads, int dh, bool dropout, int* cap, int* grid, int* walked,
                             int* xb);
 // attention_fused_bwd.hip
 bool attn_fused_bwd_supported(int heads, int dh);
 size_t attn_fused_bwd_blocks(int n_tiles, int n_chunks, int heads, int dh);
 size_t attn_fused_bwd_workspace_bytes(int64_t m, int n_tiles, int n_chunks, int heads, int dh);
-int attn_fused_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
-                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
-                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, const int32_t* chunk_item,
-                          int n_chunks, int64_t m, int heads, int dh, const float* tau, float tau_min, float* dq, float* dk,
-                          float* dv, int lddq, int lddk, int lddv, float* dtau, void* workspace, const DropoutParams& drop,
-                          hipStream_t st, int am);
+int attn_fused_bwd_launch(const AttnBwdArgs& a);
 // attention_small.hip
 bool attn_small_supported(int heads, int dh);
 size_t attn_small_blocks(int n_tiles);
-int attn_small_fwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const int32_t* tok,
-                          const int32_t* win_start, const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads,
-                          int dh, const float* tau, float tau_min, float* out, float* lse, const DropoutParams& drop,
-                          hipStream_t st, int am);
-int attn_small_bwd_launch(const float* q, const float* k, const float* v, int ldq, int ldk, int ldv, const float* out,
-                          const float* dout, const float* lse, const int32_t* tok, const int32_t* win_start,
-                          const int32_t* win_count, const int32_t* tile_item, int n_tiles, int heads, int dh,
-                          const float* tau, float tau_min, float* dq, float* dk, float* dv, int lddq, int lddk, int lddv,
-                          float* dtau, void* workspace, const DropoutParams& drop, hipStream_t st, int am);
+int attn_small_fwd_launch(const AttnArgs& a, float* out, float* lse);
+int attn_small_bwd_launch(const AttnBwdArgs& a);
 
 namespace attn {
 
@@ -52,6 +64,19 @@ constexpr float kLn2 = 0.6931471805599453f;
 //   kDot      scaled dot product (cosine_msa.py:163-165): no normalisation, scores q.k / sqrt(dh) are unbounded -- always
 //             the running maximum, no tau
 constexpr int kShared = 0, kPerHead = 1, kDot = 2;
+
+// f(std::integral_constant<int, AM>{}) for the run-time mode am: where a launcher's mode becomes a template argument.
+// (The compiler emits a file's kernels in the order their instantiations are first named: the cases keep the order the
+// launchers always had, so that the device assembly still compares equal line by line -- tools/isa_diff.py.)
+template <class F>
+int for_attn_mode(int am, F&& f) {
+    switch (am) {
+        case kPerHead: return f(std::integral_constant<int, kPerHead>{});
+        case kDot: return f(std::integral_constant<int, kDot>{});
+        case kShared: return f(std::integral_constant<int, kShared>{});
+        default: return SEG3D_EINVAL;
+    }
+}
 
 // Masking streamed tokens past a window's end INSIDE the score product: the K dimension of the score MFMAs is padded from
 // the stored head width DHS to a multiple of 32, so channel DHS is spare.  The stationary (query) fragment carries 1.0

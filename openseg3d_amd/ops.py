@@ -1746,43 +1746,39 @@ def _attn_tau_check(tau, heads, cosine=None):
         raise _lib.Seg3dError(f"window attention: tau {got} on {heads} heads; {_TAU_FORMS}")
 
 
+def _attn_entry_args(wi, m, heads, dh, tau):
+    """What the two entry sets spell differently.  One tau: seg3d_window_attn_fwd / _bwd as ever, whose window index carries
+    win_tile0; `heads` values or none: the _modes entries (per-head tau / dot product), which take (mode, tau, n_tau).
+    -> (entry suffix, window index and geometry run, tau run, flat tau or None, arguments of the workspace query)"""
+    tau_f = None if tau is None else _f32c(tau.reshape(-1))
+    size = (m, int(wi.n_tiles), heads, dh)
+    if tau_f is not None and tau_f.numel() == 1:
+        suffix, tile0, tau_run = "", (_ptr(wi.win_tile0),), (_ptr(tau_f),)
+        query = ("seg3d_window_attn_workspace_bytes",) + size
+    else:
+        mode, n_tau = (_lib.ATTN_DOT, 0) if tau_f is None else (_lib.ATTN_COSINE, tau_f.numel())
+        suffix, tile0, tau_run = "_modes", (), (mode, _ptr(tau_f), n_tau)
+        query = ("seg3d_window_attn_workspace_bytes_modes",) + size + (mode, n_tau)
+    index = (_ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count)) + tile0 + (
+        _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m, int(wi.n_windows), heads, dh)
+    return suffix, index, tau_run, tau_f, query
+
+
 def _attn_fwd_call(q, k, v, ldq, ldk, ldv, wi, m, heads, dh, tau, tau_min, drop_p, drop_seed, out, lse):
-    """One tau: seg3d_window_attn_fwd as ever; `heads` values or none: the _modes entry (per-head tau / dot product)."""
-    if tau is not None and tau.numel() == 1:
-        _lib.call("seg3d_window_attn_fwd", q, k, v, ldq, ldk, ldv,
-                  _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count), _ptr(wi.win_tile0), _ptr(wi.tile_item),
-                  int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m, int(wi.n_windows), heads, dh,
-                  _ptr(tau.reshape(-1)), float(tau_min), float(drop_p), int(drop_seed), _ptr(out), _ptr(lse), None, 0,
-                  _stream())  # (no workspace: seg3d_window_attn_workspace_bytes sizes the backward's)
-        return
-    mode, tau_f = (_lib.ATTN_DOT, None) if tau is None else (_lib.ATTN_COSINE, _f32c(tau.reshape(-1)))
-    _lib.call("seg3d_window_attn_fwd_modes", q, k, v, ldq, ldk, ldv, _ptr(wi.tok), _ptr(wi.win_start),
-              _ptr(wi.win_count), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m,
-              int(wi.n_windows), heads, dh, mode, None if tau_f is None else _ptr(tau_f), 0 if tau_f is None else tau_f.numel(),
-              float(tau_min), float(drop_p), int(drop_seed), _ptr(out), _ptr(lse), None, 0, _stream())
+    suffix, index, tau_run, _, _ = _attn_entry_args(wi, m, heads, dh, tau)
+    _lib.call("seg3d_window_attn_fwd" + suffix, q, k, v, ldq, ldk, ldv, *index, *tau_run, float(tau_min), float(drop_p),
+              int(drop_seed), _ptr(out), _ptr(lse), None, 0, _stream())  # (no workspace: the query sizes the backward's)
 
 
 def _attn_bwd_call(q, k, v, ldq, ldk, ldv, out, dout, lse, wi, m, heads, dh, tau, tau_min, drop_p, drop_seed, dq, dk, dv,
                    lddq, lddk, lddv, dev):
     """-> dtau shaped like tau (None in dot mode); written, not accumulated, by the kernels."""
-    if tau is not None and tau.numel() == 1:
-        dtau = torch.empty((1,), dtype=torch.float32, device=dev)
-        ws = _workspace(_lib.query("seg3d_window_attn_workspace_bytes", m, int(wi.n_tiles), heads, dh), dev)
-        _lib.call("seg3d_window_attn_bwd", q, k, v, ldq, ldk, ldv,
-                  _ptr(out), _ptr(dout), _ptr(lse), _ptr(wi.tok), _ptr(wi.win_start), _ptr(wi.win_count),
-                  _ptr(wi.win_tile0), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item), int(wi.n_qgroups), m,
-                  int(wi.n_windows), heads, dh, _ptr(tau.reshape(-1)), float(tau_min), float(drop_p),
-                  int(drop_seed), dq, dk, dv, lddq, lddk, lddv, _ptr(dtau), _ptr(ws), ws.numel(), _stream())
-        return dtau.reshape(tau.shape)
-    mode, tau_f = (_lib.ATTN_DOT, None) if tau is None else (_lib.ATTN_COSINE, _f32c(tau.reshape(-1)))
-    n_tau = 0 if tau_f is None else tau_f.numel()
-    dtau = None if tau_f is None else torch.empty((n_tau,), dtype=torch.float32, device=dev)
-    ws = _workspace(_lib.query("seg3d_window_attn_workspace_bytes_modes", m, int(wi.n_tiles), heads, dh, mode, n_tau), dev)
-    _lib.call("seg3d_window_attn_bwd_modes", q, k, v, ldq, ldk, ldv, _ptr(out), _ptr(dout), _ptr(lse), _ptr(wi.tok),
-              _ptr(wi.win_start), _ptr(wi.win_count), _ptr(wi.tile_item), int(wi.n_tiles), _ptr(wi.qg_item),
-              int(wi.n_qgroups), m, int(wi.n_windows), heads, dh, mode, None if tau_f is None else _ptr(tau_f), n_tau,
-              float(tau_min), float(drop_p), int(drop_seed), dq, dk, dv, lddq, lddk, lddv,
-              None if dtau is None else _ptr(dtau), _ptr(ws), ws.numel(), _stream())
+    suffix, index, tau_run, tau_f, query = _attn_entry_args(wi, m, heads, dh, tau)
+    dtau = None if tau_f is None else torch.empty((tau_f.numel(),), dtype=torch.float32, device=dev)
+    ws = _workspace(_lib.query(*query), dev)
+    _lib.call("seg3d_window_attn_bwd" + suffix, q, k, v, ldq, ldk, ldv, _ptr(out), _ptr(dout), _ptr(lse), *index, *tau_run,
+              float(tau_min), float(drop_p), int(drop_seed), dq, dk, dv, lddq, lddk, lddv, _ptr(dtau), _ptr(ws), ws.numel(),
+              _stream())
     return None if dtau is None else dtau.reshape(tau.shape)
 
 

@@ -2,6 +2,8 @@
 (cosine_msa.py:115-177) evaluated per window and head from the CSR: every head width of the model (dh 6 / 12 / 24 / 48),
 window sizes around the 16 / 32 / 128-token tile edges, tau in the fixed-maximum regime, in the online-maximum regime
 (tau < 0.036) and below tau_min (clamped), forward and backward; plus the dropout mask's statistics and determinism."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -303,6 +305,10 @@ def test_attention_time_does_not_depend_on_tau(dev):
                 for _ in range(3):
                     ops.window_attention_packed(qk, v, tau, 0.01, 8, wi)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                # The window is ten launches, under a millisecond.  The scene and the plan built above leave Python's collector
+                # about due for a full pass (50 ms with torch's objects in the heap), and when that pass fell between two of
+                # these launches the device sat idle inside the window: collect now, so that none falls due in it.
+                gc.collect()
                 torch.cuda.synchronize()
                 e0.record()
                 for _ in range(10):
