@@ -200,18 +200,6 @@ int seg3d_spconv_fwd_act_bf16(const void* x, int32_t x_bf16, const int32_t* nbr,
                               const void* w_packed, int32_t pack_flags, const float* bias,
                               const void* addend_bf16, int32_t relu, int32_t cin, int32_t cout, void* y_bf16,
                               const int32_t* row_order, void* stream);
-/* Wide layers (cin >= 192): the same contract as seg3d_spconv_fwd_act with the operand conversion hoisted out of the
- * gather-GEMM.  seg3d_spconv_presplit writes x [m_in, cin] once as bf16 hi plane | lo plane ([m_in + 1, cin] each; the
- * extra row is zero and stands for every inactive table entry) into xs (seg3d_spconv_presplit_bytes);
- * seg3d_spconv_fwd_presplit then moves rows and weights global -> LDS by LDS-DMA and multiplies: no operand passes
- * through a vector register before it is an MFMA fragment.  cin % 32 == 0, cout % 96 == 0, split-bf16 packs only.
- * Same call sites as seg3d_spconv_fwd (spconv_utils.py:13-32, pointtransformer.py:69-113, 159-166). */
-size_t seg3d_spconv_presplit_bytes(int64_t m_in, int32_t cin);
-int seg3d_spconv_presplit(const float* x, int64_t m_in, int32_t cin, void* xs, void* stream);
-int seg3d_spconv_fwd_presplit(const void* xs, const int32_t* nbr, int64_t m_out, int64_t m_in, const void* w_packed,
-                              int32_t pack_flags, const float* bias /*or NULL*/, const float* addend /*or NULL*/,
-                              int32_t relu, int32_t cin, int32_t cout, float* y,
-                              const int32_t* row_order /*or NULL*/, void* stream);
 /* a9 "row image" schedule of the same gather-GEMM for submanifold tables (spconv.SubMConv3d, call sites
  * seg3d/utils/spconv_utils.py:15-17, seg3d/models/backbones/pointtransformer.py:26-34,47-66,88-113; spconv builds the
  * equivalent "indice pairs" once per indice_key and reuses them in every layer that names the key).  A TILE PLAN is built
@@ -247,10 +235,6 @@ int seg3d_spconv_fwd_tiled_bf16(const void* x, int32_t x_bf16, const int32_t* nb
  * Same effect as the SEG3D_CONV_NBT environment variable, which is read once when the library loads.
  * The reference has no counterpart (spconv chooses its own tiles). */
 int seg3d_debug_set_conv_nbt(int32_t nbt);
-/* Test aid for the opt-in row-streaming schedule of the dense Linear layers with cin <= 192 (csrc/linear_stream.hip, the
- * nn.Linear calls of point_transformer_layer.py:260-298 / cosine_msa.py:58-63,403; bit-identical to the default schedule,
- * measured slower, SEG3D_LINEAR_STREAM=1): 1 = on, 0 = off, -1 = the environment's choice. */
-int seg3d_debug_set_linear_stream(int32_t on);
 size_t seg3d_spconv_wgrad_workspace_bytes(int64_t m_out, int32_t cin, int32_t cout);
 int seg3d_spconv_wgrad(const float* x, const float* dy, const int32_t* nbr, int64_t m_out,
                        int64_t m_in, int32_t cin, int32_t cout, int32_t flags /* bit2: split-bf16 */,
@@ -297,17 +281,12 @@ int seg3d_linear_wgrad_partials_xbf16(const uint16_t* x_bf16, const float* dy, i
                                       void* stream);
 /* ... with x = max(x_pre * scale_in[ch] + shift_in[ch], 0) formed on operand load: the training-mode BatchNorm1d + ReLU in
  * front of the Linear, from its pre-activation x_pre [m, cin] fp32 and its folded affine (seg3d_batchnorm_stats rows 4, 5).
- * Split-K kernel with the plan seg3d_linear_wgrad_partials takes for fp32 rows: the same chunks and summation order, hence
- * the same bits as seg3d_affine_act + seg3d_linear_wgrad_partials.  seg3d_linear_wgrad_bnrelu_fits = 1 when that plan is
- * the split-K kernel's (the LDS-shared and grouped A/B forms are not covered: EINVAL). */
+ * The plan of seg3d_linear_wgrad_partials: the same chunks and summation order, hence the same bits as seg3d_affine_act +
+ * seg3d_linear_wgrad_partials.  seg3d_linear_wgrad_bnrelu_fits = 1 for the shapes the entry takes (EINVAL otherwise). */
 int seg3d_linear_wgrad_bnrelu_fits(int64_t m, int32_t cin, int32_t cout);
 int seg3d_linear_wgrad_partials_bnrelu(const float* x_pre, const float* scale_in, const float* shift_in, const float* dy,
                                        int64_t m, int32_t cin, int32_t cout, int32_t with_bias, void* workspace,
                                        size_t workspace_bytes, int32_t* chunks, void* stream);
-/* A/B switch of the LDS-shared dense weight-gradient kernel (openseg3d_amd/csrc/wgrad_dense_lds.hip; OFF by default, it did
- * not win): 1 = on, 0 = off, -1 = SEG3D_WGRAD_LDS's choice.  Takes cout % 192 == 0, cin % 96 == 0, m >= 4096; the workspace
- * query covers both kernels. */
-int seg3d_debug_set_wgrad_lds(int32_t on);
 int seg3d_reduce_partials(const float* part, int32_t chunks, int64_t n, int64_t nw, float* dw, float* db, void* stream);
 int seg3d_reduce_partials_batched(const void* jobs, int32_t n_jobs, int64_t total_blocks, void* stream);
 /* a6  exact-fp32 variant for the per-point MLPs (segformer.py:21-32,58-76), whose split-bf16 forward error would land

@@ -14,7 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 ATTN_COSINE, ATTN_DOT = 0, 1  # SEG3D_ATTN_* of the header
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 56
+ABI_VERSION = 57
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -46,9 +46,6 @@ SIGNATURES = {
     "seg3d_spconv_fwd": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i32, _p, _i32, _i32, _p, _p, _p]),
     "seg3d_spconv_fwd_act": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
     "seg3d_spconv_fwd_act_bf16": (ctypes.c_int, [_p, _i32, _p, _i64, _i64, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
-    "seg3d_spconv_presplit_bytes": (_sz, [_i64, _i32]),
-    "seg3d_spconv_presplit": (ctypes.c_int, [_p, _i64, _i32, _p, _p]),
-    "seg3d_spconv_fwd_presplit": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _p]),
     "seg3d_conv_plan_bytes": (_sz, [_i64]),
     "seg3d_conv_plan_workspace_bytes": (_sz, [_i64]),
     "seg3d_conv_plan_build": (ctypes.c_int, [_p, _p, _i64, _p, _p, _sz, _p]),
@@ -56,7 +53,6 @@ SIGNATURES = {
     "seg3d_spconv_fwd_tiled": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p]),
     "seg3d_spconv_fwd_tiled_bf16": (ctypes.c_int, [_p, _i32, _p, _p, _i64, _i64, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p]),
     "seg3d_debug_set_conv_nbt": (ctypes.c_int, [_i32]),
-    "seg3d_debug_set_linear_stream": (ctypes.c_int, [_i32]),
     "seg3d_spconv_wgrad_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "seg3d_spconv_wgrad": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _i32, _i32, _p, _p, _sz, _p]),
     "seg3d_spconv_wgrad_partials": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _i32, _i32, _p, _sz, _p, _p]),
@@ -65,7 +61,6 @@ SIGNATURES = {
     "seg3d_linear_packed_bytes_f32": (ctypes.c_size_t, [_i32, _i32]),
     "seg3d_linear_pack_weight_f32": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _p]),
     "seg3d_linear_fwd_f32": (ctypes.c_int, [_p, _i64, _p, _p, _i32, _i32, _p, _p]),
-    "seg3d_debug_set_wgrad_lds": (ctypes.c_int, [_i32]),
     "seg3d_linear_packed_bytes_x6": (ctypes.c_size_t, [_i32, _i32]),
     "seg3d_linear_pack_weight_x6": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _p]),
     "seg3d_linear_fwd_x6": (ctypes.c_int, [_p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p]),

@@ -137,16 +137,9 @@ int spconv_split_fwd_io(const void* x, const int32_t* nbr, int64_t m_out, const 
                         hipStream_t st, const float* x_add);
 int spconv_split_fwd(const float* x, const int32_t* nbr, int64_t m_out, const void* wp, const float* bias,
                      const float* addend, const int32_t* row_order, int cin, int cout, float* y, int relu, hipStream_t st);
-// linear_stream.hip: the row-streaming schedule of the dense Linear layers with cin <= 192 (1 = not its shape)
-int linear_stream_fwd(const float* x, int64_t m, const void* wp, const float* bias, const float* addend, int cin, int cout,
-                      float* y, int io, hipStream_t st);
 // wgrad_split.hip: sparse-conv weight gradient.  dw == nullptr: the partial blocks only, *chunks_out = their count
 size_t wgrad_split_sparse_workspace_bytes(int64_t m_out, int cin, int cout);
 int wgrad_split_sparse(const void* x, const float* dy, const int32_t* nbr, int64_t m_out, int cin, int cout, float* dw,
                        void* workspace, size_t workspace_bytes, hipStream_t st, int32_t* chunks_out, bool x_bf16);
 // wgrad_dense.hip: the fixed-order sum of `chunks` partial blocks
 int wgrad_chunk_reduce(const float* part, int chunks, int64_t n, int64_t nw, float* dw, float* db, hipStream_t st);
-// wgrad_dense_lds.hip: the LDS-shared form for cout % 96 == 0, cin % 48 == 0 (plan returns 1 when it takes the shape)
-int wgrad_dense_lds_plan(int64_t m, int cin, int cout, int* chunks, int64_t* rows);
-int wgrad_dense_lds_launch(const float* x, const float* dy, int64_t m, int cin, int cout, int chunks, int64_t rows, float* part,
-                           int want_bias, hipStream_t st);

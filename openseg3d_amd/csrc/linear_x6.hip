@@ -12,7 +12,7 @@
 // against float64 in tests/test_gpu_dense.py: the same 1e-7-grade error as the fp32 kernel's).
 //
 // Schedule: a workgroup of 4 waves owns 256 rows x 64 columns; a wave 64 rows x 64 columns = 16 accumulator tiles.  The
-// product is taken transposed (W fragment first, as linear_stream.hip does): a lane ends up with 4 consecutive columns of one
+// product is taken transposed (W fragment first): a lane ends up with 4 consecutive columns of one
 // row per tile, the four lane groups of a row with one whole 64-byte sector per store instruction.  W's 64-column slab of a 32-channel step (three
 // planes, 12 KB) goes through LDS once per workgroup, double-buffered, one barrier per step; the rows come straight from
 // global memory into fragments (lane (c16, g): row c16 of a 16-row tile, channels 4 g .. + 3 and 16 + 4 g .. + 3 of the step:
@@ -60,8 +60,8 @@ __global__ __launch_bounds__(256) void pack_x6_kernel(const float* __restrict__ 
     dst[128] = __builtin_bit_cast(uint4, l);
 }
 
-// RT = 16-row tiles per wave (4: 256-row workgroups, two per CU; 2: 128-row workgroups, four per CU and the rows requested
-// two steps ahead), WPS = resident workgroups per CU the register allocator leaves room for.
+// RT = 16-row tiles per wave, WPS = resident workgroups per CU the register allocator leaves room for.  Launched as <2, 3>:
+// 128-row workgroups, the rows requested two steps ahead (<4, 2> and <2, 4> measured within 4 %).
 // BN (training, seg3d_linear_fwd_x6_bnrelu): the rows are the PRE-activation of a BatchNorm1d + ReLU; the eight raw channel
 // values of a step become fmaxf(v * scale_in[ch] + shift_in[ch], 0) before the split -- a multiply, an add and a max, the
 // separate affine pass's arithmetic bit for bit -- so the activated tensor is never written.  scale_in | shift_in of all
@@ -236,10 +236,6 @@ __global__ __launch_bounds__(kThreads, WPS) void linear_x6_kernel(const float* _
     }
 }
 
-// SEG3D_X6_RT (A/B): 16-row tiles per wave, 4 or 2 (default 2); SEG3D_X6_WPS: resident workgroups per CU of the 2-tile form, 3 or 4
-static const int g_x6_rt = env_int("SEG3D_X6_RT", 2) == 4 ? 4 : 2;
-static const int g_x6_wps = env_int("SEG3D_X6_WPS", 3) == 4 ? 4 : 3;
-
 }  // namespace
 
 extern "C" {
@@ -269,22 +265,12 @@ int seg3d_linear_fwd_x6(const float* x, int64_t m, const void* w_packed, const f
     if (m == 0) return SEG3D_OK;
     if (!x || !w_packed || !y) return SEG3D_EINVAL;
     const int ncg = cout >> 6;
-    const int rows = 64 * g_x6_rt;
-    const int64_t nrb = (m + rows - 1) / rows;
+    const int64_t nrb = (m + 127) / 128;
     const int64_t blocks = (nrb + 7) / 8 * 8 * ncg;
     if (blocks > 0x7FFFFFFFll) return SEG3D_EINVAL;
-    if (g_x6_rt == 4)
-        hipLaunchKernelGGL((linear_x6_kernel<4, 2>), dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), x, m,
-                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb, nullptr,
-                           nullptr);
-    else if (g_x6_wps == 4)
-        hipLaunchKernelGGL((linear_x6_kernel<2, 4>), dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), x, m,
-                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb, nullptr,
-                           nullptr);
-    else
-        hipLaunchKernelGGL((linear_x6_kernel<2, 3>), dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), x, m,
-                           static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb, nullptr,
-                           nullptr);
+    hipLaunchKernelGGL((linear_x6_kernel<2, 3>), dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), x, m,
+                       static_cast<const uint4*>(w_packed), bias, scale, shift, relu ? 1 : 0, cin, cout, y, ncg, nrb, nullptr,
+                       nullptr);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }

@@ -100,22 +100,18 @@ template <bool XB>
 __global__ __launch_bounds__(kThreads, 2) void wgrad_sparse_kernel(const void* __restrict__ x_v, const float* __restrict__ dy,
                                                                     const int32_t* __restrict__ nbr, int64_t m_rows,
                                                                     int cin, int cout, int rows_per_chunk, int nbi,
-                                                                    int tiles, int units, float* __restrict__ part,
-                                                                    int center_first) {
+                                                                    int tiles, int units, float* __restrict__ part) {
     const float* x = static_cast<const float*>(x_v);
     __shared__ __attribute__((aligned(16))) float red[64 * 64];  // block sum [co_local][ci_local]
     __shared__ int2 ring[kWaves][kRing];                         // (input row, output row) pairs
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int cq = lane & 15, rg = lane >> 4;
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    // units are dealt to the XCDs in blocks of `xcd_block` consecutive units (center_first >> 8): the offsets of one row chunk
-    // gather the same dy rows and overlapping x rows -- on ONE L2 when they are neighbours in the block
-    const int xb = (center_first >> 8) > 0 ? (center_first >> 8) : 1;
     const int qs = j / tiles, tile = j % tiles;
-    const int unit = ((qs / xb) * 8 + xcd) * xb + qs % xb;
+    const int unit = qs * 8 + xcd;  // units are dealt to the XCDs round-robin
     if (unit >= units) return;  // padding of the XCD-aligned grid (whole workgroup)
-    int chunk = unit / 27, k = unit % 27;
-    if (center_first & 1) unit_to_chunk_offset(unit, units / 27, &chunk, &k);
+    int chunk, k;
+    unit_to_chunk_offset(unit, units / 27, &chunk, &k);
     const int bi = tile % nbi, bo = tile / nbi;
     const int ci0 = bi * 64, co0 = bo * 64;
     const int64_t r_begin = (int64_t)chunk * rows_per_chunk;
@@ -273,39 +269,36 @@ __global__ __launch_bounds__(kThreads, 2) void wgrad_sparse_kernel(const void* _
 // Wide channels (C >= 128): the 64 x 64 kernel above re-reads its gathered rows once per block and is bound by that
 // L2 -> L1 stream.  Here a workgroup of 2 x 2 waves owns a 128 x 128 block of dw[:, k, :]: per 32-pair step wave w
 // loads ONE 64-channel slab (waves 0,1: dy channels co0.., co0+64..; waves 2,3: x channels ci0.., ci0+64..) with the
-// same 8-pairs x 4-channels-per-lane pattern, converts it to bf16 hi/lo records and writes them to a double-buffered
+// same 8-pairs x 4-channels-per-lane pattern, converts it to bf16 hi/lo records and writes them to an
 // LDS image [slab][hi|lo][row group][64 records] (record (c%4)*16 + c/4 of row group g = channel c, pairs 8g..8g+7,
 // conflict-free 16-B accesses both ways); after one barrier wave (wa, wb) reads slab wa as A and slab 2+wb as B and
 // issues its 48 MFMAs.  Half the operand traffic and half the conversions per MFMA.  The pair list is compacted once
 // per workgroup: each wave ballots 64 of 256 rows, wave totals are exchanged through LDS.  The slab loads of step
 // s+1 are issued before the MFMAs of step s.
+// ONE image buffer (37 KB of LDS, 162 VGPRs) and THREE workgroups per CU: a second barrier per step (all waves must have
+// read the image before the next step's rows overwrite it) against half more resident waves to hide the gathers' round
+// trips behind (the stamps say 44 % of a step is waiting for rows).  Against a double-buffered image at two workgroups
+// per CU: the 11 wide layers of the headline step 4.95 -> 4.76 ms (inverse tables -11 %, 768 -> 384 -6 %), same bits.
 constexpr int kRing2 = 512;  // pairs: at most 31 left over + 256 new
 
-// SB (round 5 experiment): ONE image buffer instead of two and three workgroups per CU instead of two -- a second barrier per
-// step (all waves must have read the image before the next step's rows overwrite it) against half more resident waves to
-// hide the gathers' round trips behind (the stamps say 44 % of a step is waiting for rows).
-template <bool XB, int DEPTH, bool SB = false>
-__global__ __launch_bounds__(kThreads, SB ? 3 : 2) void wgrad_sparse_wide_kernel(const void* __restrict__ x_v, const float* __restrict__ dy,
+template <bool XB>
+__global__ __launch_bounds__(kThreads, 3) void wgrad_sparse_wide_kernel(const void* __restrict__ x_v, const float* __restrict__ dy,
                                                                          const int32_t* __restrict__ nbr, int64_t m_rows,
                                                                          int cin, int cout, int rows_per_chunk, int nbi,
-                                                                         int tiles, int units, float* __restrict__ part,
-                                                                         int center_first) {
+                                                                         int tiles, int units, float* __restrict__ part) {
     const float* x = static_cast<const float*>(x_v);
-    __shared__ __attribute__((aligned(16))) uint4 img[SB ? 1 : 2][4][2][4][64];  // [buffer][slab][hi|lo][row group][record] 64 KiB
+    __shared__ __attribute__((aligned(16))) uint4 img[4][2][4][64];  // [slab][hi|lo][row group][record] 32 KiB
     __shared__ int2 ring[kRing2];
     __shared__ int wave_cnt[2][kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int cq = lane & 15, rg = lane >> 4;
     const int wa = wave >> 1, wb = wave & 1;
     const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    // units are dealt to the XCDs in blocks of `xcd_block` consecutive units (center_first >> 8): the offsets of one row chunk
-    // gather the same dy rows and overlapping x rows -- on ONE L2 when they are neighbours in the block
-    const int xb = (center_first >> 8) > 0 ? (center_first >> 8) : 1;
     const int qs = j / tiles, tile = j % tiles;
-    const int unit = ((qs / xb) * 8 + xcd) * xb + qs % xb;
+    const int unit = qs * 8 + xcd;  // units are dealt to the XCDs round-robin
     if (unit >= units) return;  // padding of the XCD-aligned grid (whole workgroup)
-    int chunk = unit / 27, k = unit % 27;
-    if (center_first & 1) unit_to_chunk_offset(unit, units / 27, &chunk, &k);
+    int chunk, k;
+    unit_to_chunk_offset(unit, units / 27, &chunk, &k);
     const int bi = tile % nbi, bo = tile / nbi;
     const int ci0 = bi * 128, co0 = bo * 128;
     const int64_t r_begin = (int64_t)chunk * rows_per_chunk;
@@ -363,8 +356,8 @@ __global__ __launch_bounds__(kThreads, SB ? 3 : 2) void wgrad_sparse_wide_kernel
         __syncthreads();  // ring writes visible
     };
 
-    f32x4 raw[8], raw2[DEPTH == 2 ? 8 : 1];
-    uint2 rawb[XB ? 8 : 1], rawb2[(XB && DEPTH == 2) ? 8 : 1];
+    f32x4 raw[8];
+    uint2 rawb[XB ? 8 : 1];
     // (the row format is a wave-uniform choice made ONCE per call, outside the gather loops: a branch per gathered row puts
     // every load into a basic block of its own and the waits at the block boundaries serialise the eight gathers --
     // measured: the bf16 variant ran 1.7 x SLOWER than the fp32 one that way)
@@ -396,12 +389,12 @@ __global__ __launch_bounds__(kThreads, SB ? 3 : 2) void wgrad_sparse_wide_kernel
             }
         }
     };
-    auto stash_from = [&](const f32x4* r, const uint2* rb, int buf) {
+    auto stash_from = [&](const f32x4* r, const uint2* rb) {
         if (XB && !stage_dy) {  // bf16 rows: the record is the row's own bits, there is no low plane
             if constexpr (XB) {
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj)
-                    img[buf][wave][0][rg][jj * 16 + cq] = __builtin_bit_cast(uint4, frag_from_bf16_rows(rb, jj));
+                    img[wave][0][rg][jj * 16 + cq] = __builtin_bit_cast(uint4, frag_from_bf16_rows(rb, jj));
             }
             return;
         }
@@ -412,23 +405,23 @@ __global__ __launch_bounds__(kThreads, SB ? 3 : 2) void wgrad_sparse_wide_kernel
             for (int i = 0; i < 8; ++i) v[i] = r[i][jj];
             bf16x8 hi, lo;
             split_frag(v, &hi, &lo);
-            img[buf][wave][0][rg][jj * 16 + cq] = __builtin_bit_cast(uint4, hi);
-            img[buf][wave][1][rg][jj * 16 + cq] = __builtin_bit_cast(uint4, lo);
+            img[wave][0][rg][jj * 16 + cq] = __builtin_bit_cast(uint4, hi);
+            img[wave][1][rg][jj * 16 + cq] = __builtin_bit_cast(uint4, lo);
         }
     };
     auto load_slab = [&](int h0, int valid) { load_into(raw, rawb, h0, valid); };
-    auto stash = [&](int buf) { stash_from(raw, rawb, buf); };
-    auto multiply = [&](int buf) {
+    auto stash = [&]() { stash_from(raw, rawb); };
+    auto multiply = [&]() {
         bf16x8 b_hi[4], b_lo[XB ? 1 : 4];
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            b_hi[b] = __builtin_bit_cast(bf16x8, img[buf][2 + wb][0][rg][b * 16 + cq]);
-            if constexpr (!XB) b_lo[b] = __builtin_bit_cast(bf16x8, img[buf][2 + wb][1][rg][b * 16 + cq]);
+            b_hi[b] = __builtin_bit_cast(bf16x8, img[2 + wb][0][rg][b * 16 + cq]);
+            if constexpr (!XB) b_lo[b] = __builtin_bit_cast(bf16x8, img[2 + wb][1][rg][b * 16 + cq]);
         }
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
-            const bf16x8 a_hi = __builtin_bit_cast(bf16x8, img[buf][wa][0][rg][a * 16 + cq]);
-            const bf16x8 a_lo = __builtin_bit_cast(bf16x8, img[buf][wa][1][rg][a * 16 + cq]);
+            const bf16x8 a_hi = __builtin_bit_cast(bf16x8, img[wa][0][rg][a * 16 + cq]);
+            const bf16x8 a_lo = __builtin_bit_cast(bf16x8, img[wa][1][rg][a * 16 + cq]);
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 if constexpr (XB) acc[a][b] = mfma2(a_hi, a_lo, b_hi[b], acc[a][b]);
@@ -437,112 +430,57 @@ __global__ __launch_bounds__(kThreads, SB ? 3 : 2) void wgrad_sparse_wide_kernel
         }
     };
 
-    int buf = 0;
 #ifdef SEG3D_WGRAD_STAMP
     unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long st_last = __builtin_amdgcn_s_memtime();
     const unsigned long long st_begin = st_last;
 #endif
-    if constexpr (DEPTH == 1) {
-        refill();
-        int valid = tail - head < 32 ? tail - head : 32;
-        if (valid > 0) {
-            load_slab(head, valid);
-            stash(0);
-        }
-        WSTAMP(7);
-        while (valid > 0) {
-            head += valid;
-            refill();  // also the barrier that publishes image `buf`
-            WSTAMP(0);
-            const int next = tail - head < 32 ? tail - head : 32;
-            if (next > 0) load_slab(head, next);
-            WSTAMP(1);
-            multiply(buf);
-            WSTAMP(2);
-            if constexpr (SB) {
-                __syncthreads();  // every wave has read the image: the next step's rows may overwrite it
-                if (next > 0) stash(0);
-            } else {
-                if (next > 0) stash(buf ^ 1);
-                buf ^= 1;
-            }
-            WSTAMP(3);
-            valid = next;
-#ifdef SEG3D_WGRAD_STAMP
-            st_acc[5] += 1;
-#endif
-        }
-    } else {
-        // Two steps of gathers in flight: the rows of step s+2 are requested before the MFMAs of step s and converted after
-        // the MFMAs of step s+1 (two register sets, roles alternate), so a gather has two multiplies to arrive instead of one.
-        // head = ring position of the next step to be requested; fetch() is executed by every wave alike (barriers inside).
-        auto fetch = [&](f32x4* r, uint2* rb) {
-            refill();  // (>= 32 pairs ahead or the table exhausted) + the barrier that publishes the image stashed last
-            const int v = tail - head < 32 ? tail - head : 32;
-            if (v > 0) load_into(r, rb, head, v);
-            head += v;
-            return v;
-        };
-        int va = fetch(raw, rawb);                      // step 0
-        int vb = va > 0 ? fetch(raw2, rawb2) : 0;       // step 1
-        if (va > 0) stash_from(raw, rawb, 0);
-        while (va > 0) {
-            // image `buf` = step s (from set A), set B holds the rows of step s+1
-            va = vb > 0 ? fetch(raw, rawb) : (refill(), 0);    // step s+2 into set A; its barrier publishes image `buf`
-            multiply(buf);
-            if (vb > 0) stash_from(raw2, rawb2, buf ^ 1);
-            buf ^= 1;
-            if (vb == 0) break;
-            // image `buf` = step s+1 (from set B), set A holds the rows of step s+2
-            vb = va > 0 ? fetch(raw2, rawb2) : (refill(), 0);  // step s+3 into set B
-            multiply(buf);
-            if (va > 0) stash_from(raw, rawb, buf ^ 1);
-            buf ^= 1;
-        }
+    refill();
+    int valid = tail - head < 32 ? tail - head : 32;
+    if (valid > 0) {
+        load_slab(head, valid);
+        stash();
     }
-    __syncthreads();  // all reads of the images done: reuse them as the store staging area
+    WSTAMP(7);
+    while (valid > 0) {
+        head += valid;
+        refill();  // also the barrier that publishes the image
+        WSTAMP(0);
+        const int next = tail - head < 32 ? tail - head : 32;
+        if (next > 0) load_slab(head, next);
+        WSTAMP(1);
+        multiply();
+        WSTAMP(2);
+        __syncthreads();  // every wave has read the image: the next step's rows may overwrite it
+        if (next > 0) stash();
+        WSTAMP(3);
+        valid = next;
+#ifdef SEG3D_WGRAD_STAMP
+        st_acc[5] += 1;
+#endif
+    }
+    __syncthreads();  // (the workgroup leaves the loop together)
 
     // ---- store: acc[a][b][r] = dw[co = 4*(4g + r) + a][ci = 4*c16 + b] of this wave's 64 x 64 sub-block
-    if constexpr (SB) {  // (the single image is too small to stage four blocks: 16-byte stores straight from the accumulators)
-        float* pw = part + (int64_t)chunk * ((int64_t)cout * 27 * cin);
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = co0 + 64 * wa + 4 * (4 * rg + r) + a, ci = ci0 + 64 * wb + 4 * cq;
-                if (co < cout && ci < cin)
-                    *reinterpret_cast<f32x4*>(pw + ((int64_t)co * 27 + k) * cin + ci) =
-                        (f32x4){acc[a][0][r], acc[a][1][r], acc[a][2][r], acc[a][3][r]};
-            }
-        return;
-    }
-    float* st = reinterpret_cast<float*>(&img[0][0][0][0][0]) + wave * 4096;  // 16 KiB per wave
+    // (the image is too small to stage four blocks: 16-byte stores straight from the accumulators)
+    float* pw = part + (int64_t)chunk * ((int64_t)cout * 27 * cin);
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-            *reinterpret_cast<f32x4*>(&st[(4 * (4 * rg + r) + a) * 64 + 4 * cq]) =
-                (f32x4){acc[a][0][r], acc[a][1][r], acc[a][2][r], acc[a][3][r]};
-    __builtin_amdgcn_wave_barrier();
-    float* pw = part + (int64_t)chunk * ((int64_t)cout * 27 * cin);
-    for (int e = lane; e < 64 * 16; e += 64) {
-        const int row = e >> 4, q = e & 15;
-        const int co = co0 + 64 * wa + row, ci = ci0 + 64 * wb + 4 * q;
-        if (co < cout && ci < cin)
-            *reinterpret_cast<f32x4*>(pw + ((int64_t)co * 27 + k) * cin + ci) =
-                *reinterpret_cast<const f32x4*>(&st[row * 64 + 4 * q]);
-    }
-#ifdef SEG3D_WGRAD_STAMP
-    if constexpr (DEPTH == 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        WSTAMP(4);
-        if (g_wgrad_stamp_buf && lane == 0) {
-            st_acc[6] = __builtin_amdgcn_s_memtime() - st_begin;
-            unsigned long long* o = g_wgrad_stamp_buf + (k == 13 ? 8 : 0);  // centre units apart from the rest
-            for (int i = 0; i < 8; ++i) atomicAdd(o + i, st_acc[i]);
-            atomicAdd(g_wgrad_stamp_buf + 16 + (k == 13 ? 1 : 0), 1ull);  // waves counted
+        for (int r = 0; r < 4; ++r) {
+            const int co = co0 + 64 * wa + 4 * (4 * rg + r) + a, ci = ci0 + 64 * wb + 4 * cq;
+            if (co < cout && ci < cin)
+                *reinterpret_cast<f32x4*>(pw + ((int64_t)co * 27 + k) * cin + ci) =
+                    (f32x4){acc[a][0][r], acc[a][1][r], acc[a][2][r], acc[a][3][r]};
         }
+#ifdef SEG3D_WGRAD_STAMP
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    WSTAMP(4);
+    if (g_wgrad_stamp_buf && lane == 0) {
+        st_acc[6] = __builtin_amdgcn_s_memtime() - st_begin;
+        unsigned long long* o = g_wgrad_stamp_buf + (k == 13 ? 8 : 0);  // centre units apart from the rest
+        for (int i = 0; i < 8; ++i) atomicAdd(o + i, st_acc[i]);
+        atomicAdd(g_wgrad_stamp_buf + 16 + (k == 13 ? 1 : 0), 1ull);  // waves counted
     }
 #endif
 }
@@ -562,59 +500,33 @@ int wgrad_split_sparse(const void* x, const float* dy, const int32_t* nbr, int64
     const Plan p = plan(m_out, cin, cout);
     float* part = static_cast<float*>(workspace);
     const int units = p.chunks * 27;
-    static const bool narrow_only = env_set("SEG3D_WGRAD_NARROW");  // A/B switch for profiling
-    // SEG3D_WGRAD_CENTER_FIRST (A/B): 0 = units in (chunk, offset) order (round 4)
-    // SEG3D_WGRAD_XCD_BLOCK (A/B): consecutive units per XCD (1 = round-robin, round 4's order), in bits 8 and up
-    static const int center_first = (env_int("SEG3D_WGRAD_CENTER_FIRST", 1) == 0 ? 0 : 1) |
-                                    (env_int_in("SEG3D_WGRAD_XCD_BLOCK", 1, 64, 1) << 8);
-    const int xcd_block = center_first >> 8;
-    const int unit_slots = (units + 8 * xcd_block - 1) / (8 * xcd_block) * (8 * xcd_block);  // grid padding: whole blocks on every XCD
+    const int unit_slots = (units + 7) / 8 * 8;  // grid padding: whole rounds of the eight XCDs
     // 128-wide blocks only where they add no padding (C = 256, 384, 768; not 192 = 1.5 blocks)
     const bool fits128 = ((cin + 127) / 128) * 2 == (cin + 63) / 64 && ((cout + 127) / 128) * 2 == (cout + 63) / 64;
     // ... and, padded, on the rectangular wide layers (384 <-> 192, 192 <-> 96: the strided levels' convs and the 2C -> C
     // bottlenecks): there the compaction done once per 128 x 128 block and the halved operand re-reads outweigh the padded
     // MFMAs (384 -> 192 inverse 274 -> 196 us, 192 -> 96 inverse 190 -> 151 us, 384 -> 192 submanifold 766 -> 719 us); square
-    // 192 x 192 (78 % padding on MFMA-heavy submanifold tables) loses: 395 -> 492 us.  SEG3D_WGRAD_WIDE_MIN=n (A/B) pads every
-    // layer with both widths >= n.
-    static const int wide_min = env_int("SEG3D_WGRAD_WIDE_MIN", 0);
+    // 192 x 192 (78 % padding on MFMA-heavy submanifold tables) loses: 395 -> 492 us.
     const int cmin = cin < cout ? cin : cout, cmax = cin < cout ? cout : cin;
-    const bool wide_padded = (wide_min > 0 && cmin >= wide_min) || (cin != cout && cmin >= 96 && cmax >= 192);
-    if ((fits128 || wide_padded) && !narrow_only) {
+    const bool wide_padded = cin != cout && cmin >= 96 && cmax >= 192;
+    if (fits128 || wide_padded) {
         const int nbo = (cout + 127) / 128, nbi = (cin + 127) / 128, tiles = nbo * nbi;
         const unsigned blocks = (unsigned)unit_slots * (unsigned)tiles;
-        // SEG3D_WGRAD_DEPTH (A/B): gather steps in flight per wave (1 or 2)
-        static const int depth = env_int("SEG3D_WGRAD_DEPTH", 1) == 2 ? 2 : 1;
-#define SEG3D_LAUNCH_WIDE(XB_, D_)                                                                                             \
-    hipLaunchKernelGGL((wgrad_sparse_wide_kernel<XB_, D_>), dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout, \
-                       (int)p.rows, nbi, tiles, units, part, center_first)
-        // SEG3D_WGRAD_SB (A/B): 0 = round 4's double-buffered image at two workgroups per CU.  Default 1 (round 5): ONE image
-        // buffer (37 KB of LDS, 162 VGPRs) and THREE workgroups per CU -- the kernel waits for gathered rows 44 % of the time, and
-        // half more resident waves hide more of it than the second barrier per step costs: the 11 wide layers of the headline
-        // step 4.95 -> 4.76 ms alone (inverse tables -11 %, 768 -> 384 -6 %), training step 42.95 -> 42.77 ms, same bits.
-        static const bool single = env_int("SEG3D_WGRAD_SB", 1) != 0;
-#define SEG3D_LAUNCH_WIDE_SB(XB_)                                                                                                   \
-    hipLaunchKernelGGL((wgrad_sparse_wide_kernel<XB_, 1, true>), dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout, \
-                       (int)p.rows, nbi, tiles, units, part, center_first)
-        if (single && depth == 1) {
-            if (x_bf16) SEG3D_LAUNCH_WIDE_SB(true);
-            else SEG3D_LAUNCH_WIDE_SB(false);
-        } else if (x_bf16) {  // (two register sets of both row formats do not fit: 464 bytes of scratch at depth 2)
-            SEG3D_LAUNCH_WIDE(true, 1);
-        } else {
-            if (depth == 2) SEG3D_LAUNCH_WIDE(false, 2);
-            else SEG3D_LAUNCH_WIDE(false, 1);
-        }
-#undef SEG3D_LAUNCH_WIDE_SB
-#undef SEG3D_LAUNCH_WIDE
+        if (x_bf16)
+            hipLaunchKernelGGL(wgrad_sparse_wide_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout,
+                               (int)p.rows, nbi, tiles, units, part);
+        else
+            hipLaunchKernelGGL(wgrad_sparse_wide_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout,
+                               (int)p.rows, nbi, tiles, units, part);
     } else {
         const int tiles = p.nbo * p.nbi;
         const unsigned blocks = (unsigned)unit_slots * (unsigned)tiles;
         if (x_bf16)
             hipLaunchKernelGGL(wgrad_sparse_kernel<true>, dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout,
-                               (int)p.rows, p.nbi, tiles, units, part, center_first);
+                               (int)p.rows, p.nbi, tiles, units, part);
         else
             hipLaunchKernelGGL(wgrad_sparse_kernel<false>, dim3(blocks), dim3(kThreads), 0, st, x, dy, nbr, m_out, cin, cout,
-                               (int)p.rows, p.nbi, tiles, units, part, center_first);
+                               (int)p.rows, p.nbi, tiles, units, part);
     }
     SEG3D_CHECK_LAUNCH();
     if (chunks_out) *chunks_out = p.chunks;

@@ -63,10 +63,7 @@ def side_stream(device, which=0):
     criterion; 1 = the input pipeline's (next batch's voxelization and index plan, bench.py)."""
     side = _SIDE_STREAMS.get((device.index, which))
     if side is None:
-        # SEG3D_SIDE_PRIORITY: HIP stream priority of the extra streams (the main chain is the critical path; a lower
-        # priority lets its workgroups go first where both streams have some ready)
-        prio = int(os.environ.get("SEG3D_SIDE_PRIORITY", "0"))
-        side = _SIDE_STREAMS[(device.index, which)] = torch.cuda.Stream(device=device, priority=prio)
+        side = _SIDE_STREAMS[(device.index, which)] = torch.cuda.Stream(device=device)
     return side
 
 
@@ -814,33 +811,11 @@ def debug_set_conv_nbt(nbt):
     _lib.call("seg3d_debug_set_conv_nbt", int(nbt))
 
 
-# Wide layers (cin >= 192), alternative schedule: operands pre-split once per layer, gather-GEMM fed by LDS-DMA
-# (csrc/spconv_dma.hip).  Measured on the headline scene it ties the register-staged kernel (-7 % on the 58 k-row layers,
-# +2 % on the 19 k-row layers including its conversion pass: both are bound by the 1.2 rounds of workgroups those levels
-# give 256 CUs, not by the operand path), so it is opt-in: SEG3D_CONV_DMA=1
-CONV_DMA = os.environ.get("SEG3D_CONV_DMA", "0") == "1"
-
-
-def _conv_dma_fits(packed, cin, cout):
-    return CONV_DMA and (packed.flags & PACK_SPLIT_BF16) and cin >= 192 and cin % 32 == 0 and cout % 96 == 0
-
-
-def _conv_dma(x, nbr, packed, bias, addend, relu, cin, cout, order, y):
-    m_in, m_out = x.shape[0], nbr.shape[1]
-    xs = torch.empty((_lib.query("seg3d_spconv_presplit_bytes", m_in, cin),), dtype=torch.uint8, device=x.device)
-    _lib.call("seg3d_spconv_presplit", _ptr(x), m_in, cin, _ptr(xs), _stream())
-    _lib.call("seg3d_spconv_fwd_presplit", _ptr(xs), _ptr(nbr), m_out, m_in, _ptr(packed.data), packed.flags, _ptr(bias),
-              _ptr(addend), int(bool(relu)), cin, cout, _ptr(y), _ptr(order), _stream())
-    return y
-
-
 def _conv_apply(x, nbr, packed, bias, cin, cout, order=None, plan=None):
     m_out = nbr.shape[1]
     y = torch.empty((m_out, cout), dtype=torch.float32, device=x.device)
     if _tiled_fits(plan, packed, cin, cout):
         return _conv_tiled(x, plan, packed, bias, None, False, cin, cout, y)
-    if _conv_dma_fits(packed, cin, cout):
-        return _conv_dma(x, nbr, packed, bias, None, False, cin, cout, order, y)
     _lib.call("seg3d_spconv_fwd", _ptr(x), _ptr(nbr), m_out, x.shape[0], _ptr(packed.data), packed.flags, _ptr(bias),
               cin, cout, _ptr(y), _ptr(order), _stream())
     return y
@@ -897,7 +872,7 @@ def conv_storage_bf16():
 def conv_act(x, nbr, packed, bias, cin, cout, order=None, addend=None, relu=True, plan=None):
     """act(conv(x) + bias (+ addend)) in one launch (inference form of a conv block, seg3d_spconv_fwd_act); in the bf16
     storage mode the output (and the residual it adds) is bf16, the input float32 or bf16 as it comes."""
-    if conv_storage_bf16() and not _conv_dma_fits(packed, cin, cout):
+    if conv_storage_bf16():
         # a float32 input (a SWFormer stage's output, the VFE rows, a concatenation) is rounded once here: the conv gathers
         # every row ~7-17 times, so the one conversion pass is repaid by the halved gather (dense scene, 192 -> 96 @1.2 M
         # rows: 2.9 -> 1.9 ms with bf16 rows); SEG3D_STORAGE_ROUND_INPUTS=0 keeps float32 inputs as they come
@@ -923,8 +898,6 @@ def conv_act(x, nbr, packed, bias, cin, cout, order=None, addend=None, relu=True
     addend = None if addend is None else _f32c(addend)
     if _tiled_fits(plan, packed, cin, cout):
         return _conv_tiled(x, plan, packed, bias, addend, relu, cin, cout, y)
-    if _conv_dma_fits(packed, cin, cout):
-        return _conv_dma(x, nbr, packed, bias, addend, relu, cin, cout, order, y)
     _lib.call("seg3d_spconv_fwd_act", _ptr(x), _ptr(nbr), m_out, x.shape[0], _ptr(packed.data), packed.flags, _ptr(bias),
               _ptr(addend), int(bool(relu)), cin, cout, _ptr(y), _ptr(order), _stream())
     return y

@@ -31,9 +31,6 @@ from . import ops
 
 # Inference: conv -> BatchNorm(eval) -> (+ residual) -> ReLU as one launch (seg3d_spconv_fwd_act); 0 = separate passes.
 FUSE_EVAL_BN = os.environ.get("SEG3D_FUSE_EVAL_BN", "1") != "0"
-# rows of a submanifold table processed grouped by neighbour mask inside buckets of this many rows (0 = table order,
-# -1 = one bucket); SiteLevel.mask_order
-SUBM_ORDER_BUCKET = int(os.environ.get("SEG3D_SUBM_ORDER", "0"))
 
 
 class SiteLevel:
@@ -48,7 +45,6 @@ class SiteLevel:
         self._subm = None
         self._down = None
         self._parity = None
-        self._mask_order = None
         self._subm_plan = None
         self._coarse = None  # [(coords, shape)] of the following strided levels when seeded by seed_chain()
         self._offsets = False
@@ -91,24 +87,6 @@ class SiteLevel:
         if self._subm_plan is None:
             self._subm_plan = ops.ConvPlan(self.coords, self.subm())
         return self._subm_plan
-
-    def mask_order(self):
-        """Processing order of the submanifold table's rows (int32 [M]; None = table order): inside buckets of
-        SUBM_ORDER_BUCKET consecutive rows -- spatial neighbours, whose gathered rows share cache lines -- the rows are
-        grouped by their 27-bit neighbour mask.  The gather-GEMM skips an offset for a whole 32-row wave tile / 128-row
-        workgroup tile only when none of its rows has a neighbour there: in table order a wave executes 1.4 (deep levels)
-        to 3.2 (level 1) row-products per useful one on the headline scene, grouped 1.15 - 2.2.  Scheduling only: results
-        do not depend on it."""
-        if SUBM_ORDER_BUCKET == 0:
-            return None
-        if self._mask_order is None:
-            valid = self.subm() >= 0
-            m = valid.shape[1]
-            bits = (valid.to(torch.int64) << torch.arange(27, device=valid.device, dtype=torch.int64)[:, None]).sum(0)
-            if SUBM_ORDER_BUCKET > 0:
-                bits = bits | ((torch.arange(m, device=valid.device, dtype=torch.int64) // SUBM_ORDER_BUCKET) << 27)
-            self._mask_order = torch.argsort(bits, stable=True).to(torch.int32)
-        return self._mask_order
 
     def parity_order(self):
         """Rows grouped by the parity of (z, y, x), original order kept inside a group (int32 [M]).  Under a
@@ -260,8 +238,7 @@ class SubMConv3d(_Conv3x3x3):
 
     def tables(self, x):
         nbr = x.level.subm()
-        order = x.level.mask_order()  # (the transposed table is the same table with the offsets mirrored: same grouping)
-        return nbr, nbr, ops.PACK_T_FLIP, order, order, x.level
+        return nbr, nbr, ops.PACK_T_FLIP, None, None, x.level
 
     def plans(self, x):
         plan = x.level.subm_plan()

@@ -177,7 +177,6 @@ class SparseUnet(nn.Module):
         level.seed_chain(3)
         for k in range(4):
             level.subm()
-            level.mask_order()
             level.subm_plan()
             if k >= 2:
                 level.sample_offsets()  # squeeze-excite of conv3 / conv4, OCR

@@ -90,9 +90,8 @@ def test_host_only_entry_points():
     assert cap >= 120 and list(sched) == [0, cap, 120, 2, 8, 128]
     # as many items as the cap, 8 heads each: eight rounds of the full grid
     assert lib.seg3d_window_attn_schedule(cap, cap, 8, 48, 0.0, sched) == 0 and sched[3] >= 8 and sched[2] == sched[1]
-    # both weight-gradient kernels fit the workspace the query reports; the opt-in switch validates its argument
+    # the weight-gradient kernel fits the workspace the query reports
     assert _lib.query("seg3d_linear_wgrad_workspace_bytes", 58453, 192, 192) >= 8 * (192 * 192 + 192) * 4
-    assert _lib.load().seg3d_debug_set_wgrad_lds(2) == _lib.EINVAL and _lib.load().seg3d_debug_set_wgrad_lds(-1) == 0
     # weight-gradient argument checks: every case below returns before a launch (the non-null addresses are never read)
     lib, fake, chunks = _lib.load(), ctypes.c_void_p(256), ctypes.c_int32(7)
     big = 1 << 40

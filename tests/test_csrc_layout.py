@@ -112,7 +112,7 @@ def test_cross_file_functions_are_declared_once():
             assert len(defs) == 1 and next(iter(defs)).endswith(".hip"), f"{name} is defined in {sorted(defs)}"
             assert header in _includes(next(iter(defs)), sources), f"{defs} defines {name} without seeing {header}"
             checked += 1
-    assert checked >= 25  # 13 attention launchers / queries, 12 of the conv, linear, weight-gradient, group and scan files
+    assert checked >= 22  # 11 attention launchers / queries, 11 of the conv, weight-gradient, group, scan and error files
 
 
 def test_full_wave_sums_come_from_wave_ops():

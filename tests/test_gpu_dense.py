@@ -286,55 +286,6 @@ def test_linear_with_layernorm_epilogue(m, cin, cout):
                   ops._stream())
 
 
-@pytest.mark.parametrize("m,cin,cout", [(5000, 48, 48), (5003, 48, 96), (10007, 96, 48), (70001, 96, 96), (33333, 96, 192),
-                                        (121168, 192, 96), (58453, 192, 192), (58453, 192, 384), (4099, 192, 576), (15, 192, 192),
-                                        (1, 48, 144), (20000, 128, 96), (20000, 64, 48)])
-def test_row_streaming_linear_is_bit_identical_to_the_gather_gemm_case(m, cin, cout):
-    """(The schedule is OFF by default -- it lost the A/B, csrc/linear_stream.hip -- and is pinned here through the debug
-    switch so that the opt-in stays correct.)  Round 5's schedule of the dense Linear layers with cin <= 192 (csrc/linear_stream.hip: W block resident in LDS, every
-    wave streams its own 16-row tiles with a rolling prefetch, quad-transposed 16-byte stores) against the schedule it
-    replaces (the gather-GEMM's single-offset case, forced through the column-width switch): same products in the same order,
-    so the results agree BIT FOR BIT -- plain, with bias, with a residual addend and with the elementwise factor of fc2's
-    input gradient (seg3d_linear_fwd_mul) -- and both agree with fp64 within the split-bf16 tolerance."""
-    from openseg3d_amd import _lib, ops
-    dev = torch.device("cuda:0")
-    gen = torch.Generator().manual_seed(m * 7 + cin + cout)
-    x = torch.randn(m, cin, generator=gen).to(dev)
-    w = (torch.randn(cout, cin, generator=gen) / cin ** 0.5).to(dev)
-    b = torch.randn(cout, generator=gen).to(dev)
-    add = torch.randn(m, cout, generator=gen).to(dev)
-    packed = ops._linear_pack(w, False)
-    old_nbt = {48: 3, 96: 6, 144: 3, 192: 12, 384: 12, 576: 12}[cout]
-
-    def run(bias, addend, mul):
-        y = torch.full((m, cout), float("nan"), device=dev)
-        if mul:
-            _lib.call("seg3d_linear_fwd_mul", ops._ptr(x), m, ops._ptr(packed), ops._ptr(addend), cin, cout, ops._ptr(y), ops._stream())
-        else:
-            _lib.call("seg3d_linear_fwd", ops._ptr(x), m, ops._ptr(packed), ops._ptr(bias), ops._ptr(addend), cin, cout, ops._ptr(y),
-                      ops._stream())
-        return y
-
-    for bias, addend, mul in ((None, None, False), (b, None, False), (b, add, False), (None, add, True)):
-        _lib.call("seg3d_debug_set_linear_stream", 1)
-        try:
-            new = run(bias, addend, mul)
-        finally:
-            _lib.call("seg3d_debug_set_linear_stream", -1)  # back to the environment's choice
-        ops.debug_set_conv_nbt(old_nbt)  # a forced column width keeps the dense case on the gather-GEMM kernel
-        try:
-            old = run(bias, addend, mul)
-        finally:
-            ops.debug_set_conv_nbt(0)
-        assert torch.equal(new, old), (bias is not None, addend is not None, mul, float((new - old).abs().max()))
-        ref = x.double() @ w.double().t()
-        if bias is not None:
-            ref = ref + b.double()
-        if addend is not None:
-            ref = ref * add.double() if mul else ref + add.double()
-        assert float((new.double() - ref).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
-
-
 @pytest.mark.parametrize("m,cin,cout", [(174633, 128, 256), (70001, 256, 64), (5000, 64, 128), (4099, 96, 256), (257, 256, 128),
                                         (255, 64, 64), (1, 32, 64), (20000, 128, 64)])
 def test_six_product_linear_is_fp32_grade(m, cin, cout):
@@ -413,40 +364,3 @@ def test_eval_point_mlp_runs_linear_batchnorm_relu_as_one_launch():
     y = mlp(x.requires_grad_())
     y.sum().backward()
     assert x.grad is not None and torch.isfinite(x.grad).all()
-
-
-@pytest.mark.parametrize("m,cin,cout", [(58453, 192, 192), (40001, 96, 192), (20011, 384, 384), (9999, 192, 384), (12345, 384, 768),
-                                        (4096, 96, 192), (5000, 288, 576)])
-def test_lds_shared_dense_weight_gradient_matches_fp64_and_is_reproducible(m, cin, cout):
-    """The opt-in LDS-shared form of the Linear weight gradient (csrc/wgrad_dense_lds.hip: OFF by default, it did not win; pinned
-    through the debug switch): dW and db against float64 within the split-bf16 tolerance, bit-identical run to run (partial
-    blocks + fixed-order sum, no atomics), ragged last steps and a last chunk shorter than the others."""
-    from openseg3d_amd import _lib, ops
-    dev = torch.device("cuda:0")
-    gen = torch.Generator().manual_seed(m + cin)
-    x = torch.randn(m, cin, generator=gen).to(dev)
-    dy = torch.randn(m, cout, generator=gen).to(dev)
-    ref_w = dy.double().t() @ x.double()
-    ref_b = dy.double().sum(0)
-
-    def run():
-        dw = torch.full((cout, cin), float("nan"), device=dev)
-        db = torch.full((cout,), float("nan"), device=dev)
-        nb = _lib.query("seg3d_linear_wgrad_workspace_bytes", m, cin, cout)
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-        _lib.call("seg3d_linear_wgrad", ops._ptr(x), ops._ptr(dy), m, cin, cout, ops._ptr(dw), ops._ptr(db), ops._ptr(ws), nb,
-                  ops._stream())
-        return dw, db
-
-    old_w, old_b = run()
-    _lib.call("seg3d_debug_set_wgrad_lds", 1)
-    try:
-        dw, db = run()
-        dw2, db2 = run()
-    finally:
-        _lib.call("seg3d_debug_set_wgrad_lds", -1)
-    assert torch.equal(dw, dw2) and torch.equal(db, db2)
-    scale = float(ref_w.abs().max())
-    assert float((dw.double() - ref_w).abs().max()) < 1e-4 * scale
-    assert float((old_w.double() - ref_w).abs().max()) < 1e-4 * scale
-    assert float((db.double() - ref_b).abs().max()) < 1e-4 * float(ref_b.abs().max())

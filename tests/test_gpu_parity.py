@@ -266,8 +266,8 @@ def headline_sites(dev):
 
 
 @pytest.mark.parametrize("cin,cout,nbt", [(cin, cout, nbt) for cin, cout in [(96, 192), (192, 192), (384, 192)]
-                                          for nbt in (12, 6, "dma")] + [(192, 384, 8)])
-def test_sparse_conv_wide_tiles_at_benchmark_row_counts(dev, headline_sites, monkeypatch, cin, cout, nbt):
+                                          for nbt in (12, 6)] + [(192, 384, 8)])
+def test_sparse_conv_wide_tiles_at_benchmark_row_counts(dev, headline_sites, cin, cout, nbt):
     """Value parity of the column-block instantiations the benchmark's deep layers run (NBT = 12: cout % 192 == 0 and
     >= 400 row tiles; NBT = 8: the 128-column tiles of the 384-wide 19 k-row level; NBT = 6: 96-column tiles), on
     >= 51 200 rows, for the submanifold,
@@ -275,9 +275,6 @@ def test_sparse_conv_wide_tiles_at_benchmark_row_counts(dev, headline_sites, mon
     oracle.  Same tolerances as test_sparse_conv_forward_and_backward (split-bf16: ~2^-16 relative per product)."""
     from oracle import sparse_conv as sc
     from openseg3d_amd import ops, spconv
-    if nbt == "dma":  # the LDS-DMA schedule of the wide layers (csrc/spconv_dma.hip, opt-in): same contract, same bar
-        monkeypatch.setattr(ops, "CONV_DMA", True)
-        nbt = 0
     coords, shape, ref = headline_sites
     m = coords.shape[0]
     assert m >= 51200
@@ -832,25 +829,3 @@ def test_class_context_matches_the_reference_loop(dev, rows):
     again = ops.class_context(fg, pg, offsets, scale)
     again.backward(g.to(dev))
     assert torch.equal(first[0], again) and torch.equal(first[1], fg.grad) and torch.equal(first[2], pg.grad)
-
-
-def test_opt_in_conv_schedules_change_no_bit(dev, tmp_path):
-    """The gather-GEMM's opt-in schedules -- submanifold rows grouped by neighbour mask (SEG3D_SUBM_ORDER) and two chunks in
-    flight on the narrow layers (SEG3D_CONV_DEPTH=2), both measured slower and off by default -- reorder work, never
-    arithmetic: forward, input gradient and weight gradient of three layers are bit-identical to the default schedule's.
-    (The switches are read at import / library load, hence child processes.)"""
-    import subprocess
-    import sys
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_conv_switch_child.py")
-    outs = {}
-    for tag, env in (("default", {}), ("grouped", {"SEG3D_SUBM_ORDER": "512", "SEG3D_CONV_DEPTH": "2"}),
-                     ("one_bucket", {"SEG3D_SUBM_ORDER": "-1"})):
-        path = str(tmp_path / f"{tag}.pt")
-        run = subprocess.run([sys.executable, child, path], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-        assert run.returncode == 0, run.stderr[-2000:]
-        outs[tag] = torch.load(path)
-    assert int(outs["default"]["order0"]) == 0 and int(outs["grouped"]["order0"]) > 0
-    for tag in ("grouped", "one_bucket"):
-        for k, v in outs["default"].items():
-            if not k.startswith("order"):
-                assert torch.equal(v, outs[tag][k]), (tag, k)

@@ -28,9 +28,9 @@ bench("torch.cuda.current_stream().cuda_stream", lambda: torch.cuda.current_stre
 bench("torch._C._cuda_getCurrentRawStream(0)", lambda: torch._C._cuda_getCurrentRawStream(0))
 bench("ops._ptr(t)", lambda: ops._ptr(t))
 bench("t.data_ptr()", t.data_ptr)
-bench("_lib.call(host-only entry, 1 arg)", lambda: _lib.call("seg3d_debug_set_wgrad_lds", -1))
-fn = lib.seg3d_debug_set_wgrad_lds
-bench("bound ctypes function, 1 arg", lambda: fn(-1))
+bench("_lib.call(host-only entry, 1 arg)", lambda: _lib.call("seg3d_debug_set_conv_nbt", 0))
+fn = lib.seg3d_debug_set_conv_nbt
+bench("bound ctypes function, 1 arg", lambda: fn(0))
 f11 = lib.seg3d_linear_fwd_x6
 args_obj = (ops._ptr(t), 0, ops._ptr(t), None, None, None, 0, 128, 256, ops._ptr(t), ops._stream())
 bench("ctypes call, 11 args prebuilt c_void_p (m = 0: returns at once)", lambda: f11(*args_obj))

@@ -6,7 +6,6 @@ O=gpurun_out/r5f; mkdir -p $O
 if [ "$1" = "a" ]; then
 python bench.py --full > $O/default.json 2> $O/default.err; echo default rc=$?
 python bench.py --full --mode fwd --steps 20 --warmup 5 --no-cpu-baseline > $O/fwd.json 2> $O/fwd.err; echo fwd rc=$?
-SEG3D_WGRAD_CENTER_FIRST=0 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-fp32-exact > $O/no_centre_first.json 2> $O/no_centre_first.err; echo no_centre_first rc=$?
 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-fp32-exact > $O/default_b.json 2> $O/default_b.err; echo default_b rc=$?
 SEG3D_WGRAD_DEFER=0 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-fp32-exact > $O/nodefer.json 2> $O/nodefer.err; echo nodefer rc=$?
 SEG3D_POINT_MLP=fp32 python bench.py --full --steps 15 --warmup 4 --no-cpu-baseline --no-fp32-exact > $O/default_f32mlp.json 2> $O/default_f32mlp.err; echo f32mlp rc=$?
