@@ -1422,6 +1422,53 @@ int seg3d_point_image_features_host(const seg3d_feature_map_table* table, const 
                                     int64_t n, int32_t stride, int32_t cp_col, float* out_dense, int32_t* out_camera,
                                     int32_t* n_outside);
 
+/* Optimizer step (tools/train.py:136-149 optimizer.step(); builder.py:43-54: AdamW or SGD with momentum): every float32
+ * parameter of a model updated by ONE launch.  `table` is an array of n_tensors records sorted by first_block (DEVICE
+ * memory for seg3d_optim_step, HOST memory with host pointers for seg3d_optim_step_host); tensor i covers workgroups
+ * [first_block_i, first_block_{i+1}) of seg3d_optim_block_elems() elements each (ceil(count / block_elems) of them; a
+ * tensor with count == 0 owns none and is never touched), total_blocks is their sum.  A workgroup finds its tensor by
+ * bisection and updates one chunk; tensors whose param, grad and state pointers are all 16-byte aligned move as
+ * 16-byte vectors, the others (gradient views at an arbitrary 4-byte offset) and the tails element by element.
+ * No atomics, no LDS, no allocation, no synchronisation.
+ * `hyper` is a HOST array of n_hyper <= SEG3D_OPTIM_MAX_HYPER scalar sets; it is copied into the kernel arguments, so
+ * the values may change every step without an upload.  record.hyper indexes it.  The arithmetic, in this order of
+ * float32 operations (torch's single-tensor algorithms; no fused multiply-add anywhere, divide and sqrt correctly
+ * rounded, so the device entry and the host entry give the same bits):
+ *   SEG3D_OPTIM_SGD    v = {lr, wd, mu}: g' = g + wd * p (skipped when wd == 0); with state0 (momentum buffer):
+ *                      m = g' when flags has SEG3D_OPTIM_FIRST_STEP, else m = mu * m + g'; p = p - lr * m.
+ *                      state0 == NULL: p = p - lr * g'.  state1 is ignored.
+ *   SEG3D_OPTIM_ADAMW  v = {1 - lr * wd, 1 - beta1, beta2, 1 - beta2, lr / bc1, sqrt(bc2), eps}, bc_i = 1 - beta_i^step:
+ *                      p = p * v0; m = m + (g - m) * v1; v = v * v2 + v3 * g * g; p = p - v4 * m / (sqrt(v) / v5 + v6);
+ *                      state0 = m (exp_avg), state1 = v (exp_avg_sq), both required.
+ * SEG3D_EINVAL before any launch: table NULL with n_tensors > 0, hyper NULL with n_hyper > 0, a negative count,
+ * n_hyper > SEG3D_OPTIM_MAX_HYPER, n_hyper == 0 with n_tensors > 0, total_blocks outside [0, INT32_MAX], an unknown
+ * algo.  n_tensors == 0 or total_blocks == 0 returns 0 and does nothing.  The host entry also checks every record
+ * (NULL param / grad with count > 0, missing AdamW state, hyper index out of range, first_block out of order); the
+ * device entry cannot read its table, the kernel skips a record whose hyper index is out of range. */
+#define SEG3D_OPTIM_SGD 0
+#define SEG3D_OPTIM_ADAMW 1
+#define SEG3D_OPTIM_MAX_HYPER 8
+#define SEG3D_OPTIM_FIRST_STEP 1
+typedef struct {
+  float* param;
+  const float* grad;
+  float* state0;        /* momentum_buffer / exp_avg, or NULL */
+  float* state1;        /* exp_avg_sq, or NULL */
+  int64_t count;        /* elements */
+  int64_t first_block;
+  int32_t hyper;        /* index into the hyper sets of the call */
+  int32_t flags;        /* SEG3D_OPTIM_FIRST_STEP */
+  int64_t reserved;
+} seg3d_optim_tensor;   /* 64 bytes */
+typedef struct {
+  float v[8];
+} seg3d_optim_hyper;    /* 32 bytes */
+int32_t seg3d_optim_block_elems(void);
+int seg3d_optim_step(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks,
+                     const seg3d_optim_hyper* hyper, int32_t n_hyper, int32_t algo, void* stream);
+int seg3d_optim_step_host(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks,
+                          const seg3d_optim_hyper* hyper, int32_t n_hyper, int32_t algo);
+
 #ifdef __cplusplus
 }
 #endif

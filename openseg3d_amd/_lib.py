@@ -14,7 +14,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "seg3d_hip.h")
 OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 ATTN_COSINE, ATTN_DOT = 0, 1  # SEG3D_ATTN_* of the header
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
-ABI_VERSION = 57
+OPTIM_SGD, OPTIM_ADAMW, OPTIM_MAX_HYPER, OPTIM_FIRST_STEP = 0, 1, 8, 1  # SEG3D_OPTIM_* of the header
+ABI_VERSION = 58
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -209,6 +210,9 @@ SIGNATURES = {
     "seg3d_range_image_labels_host": (ctypes.c_int, [_p, _i32, _p, _i64, _i32, _i32, _i32, _p, _p, _p]),
     "seg3d_point_image_features": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p, _p]),
     "seg3d_point_image_features_host": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
+    "seg3d_optim_block_elems": (_i32, []),
+    "seg3d_optim_step": (ctypes.c_int, [_p, _i32, _i64, _p, _i32, _i32, _p]),
+    "seg3d_optim_step_host": (ctypes.c_int, [_p, _i32, _i64, _p, _i32, _i32]),
 }
 
 _ERR = {EINVAL: "SEG3D_EINVAL (bad argument)", EWORKSPACE: "SEG3D_EWORKSPACE (workspace too small)",
