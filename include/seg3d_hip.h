@@ -1469,6 +1469,35 @@ int seg3d_optim_step(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t
 int seg3d_optim_step_host(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks,
                           const seg3d_optim_hyper* hyper, int32_t n_hyper, int32_t algo);
 
+/* Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) between loss.backward() and optimizer.step(), over
+ * the same record table and workgroup geometry as the step.  For these entries record.param is the GRADIENT array (read
+ * by the norm, written by the scale); grad, state0, state1, hyper and flags are ignored and may be 0; count and
+ * first_block mean what they mean for seg3d_optim_step.
+ *   seg3d_grad_norm   two launches.  (1) one workgroup per chunk: every thread adds (double)g * (double)g (exact in
+ *                     fp64) in a fixed order, the workgroup's sum goes to workspace[block] as one double; (2) one
+ *                     workgroup adds the partials in a fixed order and writes result[0] = (float)sqrt(total) and
+ *                     result[1] = c, c = max_norm / (result[0] + 1e-6f) in float32, replaced by 1.0f when c > 1.0f (a NaN
+ *                     c stays NaN): torch's clip coefficient.  max_norm = +inf: the norm alone (c = 1 unless the norm is
+ *                     not finite).  No atomics: the same bits on every run.  The sum of squares in fp64 is within
+ *                     (n - 1) * 2^-53 of exact whatever the order, and squares that overflow or underflow float32 do not.
+ *   seg3d_grad_scale  one launch on the same grid: a workgroup reads *coef (DEVICE memory, normally result + 1) and
+ *                     returns when it is 1.0f, else g = g * coef over its chunk (a NaN coefficient is not 1).
+ *   seg3d_grad_norm_workspace_bytes   8 bytes per workgroup; a smaller workspace_bytes is SEG3D_EWORKSPACE.
+ *   seg3d_grad_norm_host / seg3d_grad_scale_host   the same definitions in plain C++ over HOST pointers (table, arrays,
+ *                     result, coef): the twin the device is compared with and the path of CPU parameters.  They also check
+ *                     every record: NULL array with count > 0, negative count, first_block out of order, wrong block sum.
+ * SEG3D_EINVAL before any launch: table NULL with n_tensors > 0, NULL result / coef, n_tensors < 0, total_blocks outside
+ * [0, INT32_MAX], a negative or NaN max_norm, workspace NULL with total_blocks > 0.  n_tensors == 0 or total_blocks == 0:
+ * the norm entries write norm 0 and coefficient 1 and return 0, the scale entries do nothing. */
+size_t seg3d_grad_norm_workspace_bytes(int64_t total_blocks);
+int seg3d_grad_norm(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, float max_norm,
+                    void* workspace, size_t workspace_bytes, float* result, void* stream);
+int seg3d_grad_scale(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, const float* coef,
+                     void* stream);
+int seg3d_grad_norm_host(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, float max_norm,
+                         float* result);
+int seg3d_grad_scale_host(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, const float* coef);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ OK, EINVAL, EWORKSPACE, ELAUNCH = 0, -1, -2, -3
 ATTN_COSINE, ATTN_DOT = 0, 1  # SEG3D_ATTN_* of the header
 REDUCE_SUM, REDUCE_MEAN, REDUCE_MAX = 0, 1, 2
 OPTIM_SGD, OPTIM_ADAMW, OPTIM_MAX_HYPER, OPTIM_FIRST_STEP = 0, 1, 8, 1  # SEG3D_OPTIM_* of the header
-ABI_VERSION = 58
+ABI_VERSION = 59
 
 _p, _i32, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 _u64 = ctypes.c_uint64
@@ -213,6 +213,11 @@ SIGNATURES = {
     "seg3d_optim_block_elems": (_i32, []),
     "seg3d_optim_step": (ctypes.c_int, [_p, _i32, _i64, _p, _i32, _i32, _p]),
     "seg3d_optim_step_host": (ctypes.c_int, [_p, _i32, _i64, _p, _i32, _i32]),
+    "seg3d_grad_norm_workspace_bytes": (_sz, [_i64]),
+    "seg3d_grad_norm": (ctypes.c_int, [_p, _i32, _i64, _f, _p, _sz, _p, _p]),
+    "seg3d_grad_scale": (ctypes.c_int, [_p, _i32, _i64, _p, _p]),
+    "seg3d_grad_norm_host": (ctypes.c_int, [_p, _i32, _i64, _f, _p]),
+    "seg3d_grad_scale_host": (ctypes.c_int, [_p, _i32, _i64, _p]),
 }
 
 _ERR = {EINVAL: "SEG3D_EINVAL (bad argument)", EWORKSPACE: "SEG3D_EWORKSPACE (workspace too small)",

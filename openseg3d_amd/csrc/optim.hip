@@ -1,8 +1,11 @@
 // Optimizer step: SGD (momentum) and AdamW over every parameter tensor of a model in one launch.
 // A pure stream: per element 3 reads + 2 writes (SGD with momentum, 20 B) or 4 reads + 3 writes (AdamW, 28 B); no
 // atomics, no LDS.  The arithmetic is optim_update.hpp's, shared with the host twin at the bottom of this file.
+// Beside the step, on the same table and grid: the global L2 norm of the gradients summed in fp64, and the clip by it
+// (seg3d_grad_norm / seg3d_grad_scale).
 #include "common.hpp"
 #include "optim_update.hpp"
+#include "wave_ops.hpp"
 
 static_assert(sizeof(seg3d_optim_tensor) == 64, "seg3d_optim_tensor layout is part of the C ABI (seg3d_optim_step)");
 static_assert(sizeof(seg3d_optim_hyper) == 32, "seg3d_optim_hyper layout is part of the C ABI (seg3d_optim_step)");
@@ -130,11 +133,207 @@ void host_step(const seg3d_optim_tensor* table, int32_t n_tensors, const seg3d_o
     }
 }
 
+// ---------------------------------------------------------------- gradient-norm clipping
+// The same table and grid as the step; record.param is the gradient array.  Norm: one fp64 partial per workgroup, then one
+// workgroup over the partials; scale: g = g * coef unless the coefficient is 1.  No atomics: the same bits on every run.
+typedef __attribute__((address_space(1))) float gfloat;
+
+// last tensor with first_block <= blockIdx.x (the bisection of optim_step_kernel)
+__device__ __forceinline__ int tensor_of_block(const seg3d_optim_tensor* __restrict__ table, int n_tensors) {
+    int lo = 0, hi = n_tensors - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].first_block <= (int64_t)blockIdx.x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__host__ __device__ inline double square64(float g) {  // exact: 24 x 24 significand bits, and no float32 range limit
+    const double d = (double)g;
+    return d * d;
+}
+
+// {norm, clip coefficient} from the sum of squares: torch's max_norm / (total_norm + 1e-6) clamped at 1, in float32
+__host__ __device__ inline void norm_result(double total, float max_norm, bool nothing, float* result) {
+    const float norm = (float)sqrt(total);
+    float c = max_norm / (norm + 1e-6f);
+    if (c > 1.0f || nothing) c = 1.0f;  // a NaN c stays NaN
+    result[0] = norm;
+    result[1] = c;
+}
+
+__global__ __launch_bounds__(kThreads) void grad_norm_partial_kernel(const seg3d_optim_tensor* __restrict__ table,
+                                                                      int n_tensors, double* __restrict__ partials) {
+    const seg3d_optim_tensor r = table[tensor_of_block(table, n_tensors)];
+    const int64_t start = ((int64_t)blockIdx.x - r.first_block) * kBlockElems;
+    const int tid = threadIdx.x;
+    double acc = 0.0;
+    if (start >= 0 && start < r.count) {  // (no early return: every thread reaches the workgroup sum)
+        const int n_here = (int)(r.count - start < kBlockElems ? r.count - start : kBlockElems);
+        const float* g = r.param + start;
+        if (((uintptr_t)g & 15) != 0) {  // a gradient view at a 4-byte offset
+            const gfloat* g1 = (const gfloat*)g;
+            for (int i = tid; i < n_here; i += kThreads) acc += square64(g1[i]);
+        } else {
+            const gvec* g4 = (const gvec*)g;
+            if (n_here == kBlockElems) {  // a full chunk: every load issued before the first use
+                vec4 gv[kUnroll];
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) gv[u] = g4[u * kThreads + tid];
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc += square64(gv[u][j]);
+            } else {
+                const int n_vec = n_here >> 2;
+                for (int v = tid; v < n_vec; v += kThreads) {
+                    const vec4 gv = g4[v];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc += square64(gv[j]);
+                }
+                const int i = n_vec * 4 + tid;  // the last count % 4 elements
+                if (i < n_here) acc += square64(((const gfloat*)g)[i]);
+            }
+        }
+    }
+    const double total = block_sum<kThreads, double>(acc);
+    if (tid == 0) partials[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kThreads) void grad_norm_final_kernel(const double* __restrict__ partials, int n_partials,
+                                                                    float max_norm, float* __restrict__ result) {
+    // thread t adds partials t, t + 256, ... in ascending order; 16 loads are in flight before the first add (one load
+    // per add: 9.4 us for the model's 8041 partials, all of it latency).  Past the end a +0.0 is added: the same bits.
+    constexpr int kBatch = 16;
+    double acc = 0.0;
+    for (int64_t base = threadIdx.x; base < n_partials; base += (int64_t)kBatch * kThreads) {
+        double v[kBatch];
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) {
+            const int64_t i = base + (int64_t)u * kThreads;
+            v[u] = i < n_partials ? partials[i] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) acc += v[u];
+    }
+    const double total = block_sum<kThreads, double>(acc);
+    if (threadIdx.x == 0) norm_result(total, max_norm, n_partials == 0, result);
+}
+
+__global__ __launch_bounds__(kThreads) void grad_scale_kernel(const seg3d_optim_tensor* __restrict__ table, int n_tensors,
+                                                               const float* __restrict__ coef) {
+    const float c = *coef;
+    if (c == 1.0f) return;  // the healthy run: nothing is read or written (a NaN coefficient is not 1)
+    const seg3d_optim_tensor r = table[tensor_of_block(table, n_tensors)];
+    const int64_t start = ((int64_t)blockIdx.x - r.first_block) * kBlockElems;
+    if (start < 0 || start >= r.count) return;
+    const int n_here = (int)(r.count - start < kBlockElems ? r.count - start : kBlockElems);
+    float* g = r.param + start;
+    const int tid = threadIdx.x;
+    if (((uintptr_t)g & 15) != 0) {
+        gfloat* g1 = (gfloat*)g;
+        for (int i = tid; i < n_here; i += kThreads) g1[i] = g1[i] * c;
+        return;
+    }
+    gvec* g4 = (gvec*)g;
+    if (n_here == kBlockElems) {
+        vec4 gv[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) gv[u] = g4[u * kThreads + tid];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) g4[u * kThreads + tid] = gv[u] * c;
+        return;
+    }
+    const int n_vec = n_here >> 2;
+    for (int v = tid; v < n_vec; v += kThreads) {
+        const vec4 gv = g4[v];
+        g4[v] = gv * c;
+    }
+    const int i = n_vec * 4 + tid;
+    if (i < n_here) ((gfloat*)g)[i] = ((gfloat*)g)[i] * c;
+}
+
+int check_grad_call(const void* table, int32_t n_tensors, int64_t total_blocks) {
+    if (n_tensors < 0 || total_blocks < 0 || total_blocks > 0x7FFFFFFF) return SEG3D_EINVAL;
+    if (n_tensors > 0 && !table) return SEG3D_EINVAL;
+    return SEG3D_OK;
+}
+
+// what the device entries cannot do: read the table
+int check_grad_records(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks) {
+    int64_t next_block = 0;
+    for (int32_t t = 0; t < n_tensors; ++t) {
+        const seg3d_optim_tensor& r = table[t];
+        if (r.count < 0 || r.first_block != next_block || (r.count > 0 && !r.param)) return SEG3D_EINVAL;
+        next_block += ceil_div64(r.count, kBlockElems);
+    }
+    return next_block == total_blocks ? SEG3D_OK : SEG3D_EINVAL;
+}
+
 }  // namespace
 
 extern "C" {
 
 int32_t seg3d_optim_block_elems(void) { return kBlockElems; }
+
+size_t seg3d_grad_norm_workspace_bytes(int64_t total_blocks) {
+    return total_blocks > 0 ? (size_t)total_blocks * sizeof(double) : 0;
+}
+
+int seg3d_grad_norm(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, float max_norm,
+                    void* workspace, size_t workspace_bytes, float* result, void* stream) {
+    if (const int rc = check_grad_call(table, n_tensors, total_blocks); rc != SEG3D_OK) return rc;
+    if (!result || !(max_norm >= 0.0f)) return SEG3D_EINVAL;  // (a NaN max_norm fails the comparison)
+    const bool nothing = n_tensors == 0 || total_blocks == 0;
+    if (!nothing) {
+        if (!workspace) return SEG3D_EINVAL;
+        if (workspace_bytes < seg3d_grad_norm_workspace_bytes(total_blocks)) return SEG3D_EWORKSPACE;
+        hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)total_blocks), dim3(kThreads), 0, as_stream(stream),
+                           table, (int)n_tensors, (double*)workspace);
+        SEG3D_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(kThreads), 0, as_stream(stream), (const double*)workspace,
+                       nothing ? 0 : (int)total_blocks, max_norm, result);
+    SEG3D_CHECK_LAUNCH();
+    return SEG3D_OK;
+}
+
+int seg3d_grad_scale(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, const float* coef,
+                     void* stream) {
+    if (const int rc = check_grad_call(table, n_tensors, total_blocks); rc != SEG3D_OK) return rc;
+    if (!coef) return SEG3D_EINVAL;
+    if (n_tensors == 0 || total_blocks == 0) return SEG3D_OK;
+    hipLaunchKernelGGL(grad_scale_kernel, dim3((unsigned)total_blocks), dim3(kThreads), 0, as_stream(stream), table,
+                       (int)n_tensors, coef);
+    SEG3D_CHECK_LAUNCH();
+    return SEG3D_OK;
+}
+
+int seg3d_grad_norm_host(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, float max_norm,
+                         float* result) {
+    if (const int rc = check_grad_call(table, n_tensors, total_blocks); rc != SEG3D_OK) return rc;
+    if (!result || !(max_norm >= 0.0f)) return SEG3D_EINVAL;
+    if (n_tensors > 0)
+        if (const int rc = check_grad_records(table, n_tensors, total_blocks); rc != SEG3D_OK) return rc;
+    double total = 0.0;
+    for (int32_t t = 0; t < n_tensors; ++t)
+        for (int64_t i = 0; i < table[t].count; ++i) total += square64(table[t].param[i]);
+    norm_result(total, max_norm, n_tensors == 0 || total_blocks == 0, result);
+    return SEG3D_OK;
+}
+
+int seg3d_grad_scale_host(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks, const float* coef) {
+    if (const int rc = check_grad_call(table, n_tensors, total_blocks); rc != SEG3D_OK) return rc;
+    if (!coef) return SEG3D_EINVAL;
+    if (n_tensors == 0) return SEG3D_OK;
+    if (const int rc = check_grad_records(table, n_tensors, total_blocks); rc != SEG3D_OK) return rc;
+    const float c = *coef;
+    if (c == 1.0f) return SEG3D_OK;
+    for (int32_t t = 0; t < n_tensors; ++t)
+        for (int64_t i = 0; i < table[t].count; ++i) table[t].param[i] = table[t].param[i] * c;
+    return SEG3D_OK;
+}
 
 int seg3d_optim_step(const seg3d_optim_tensor* table, int32_t n_tensors, int64_t total_blocks,
                      const seg3d_optim_hyper* hyper, int32_t n_hyper, int32_t algo, void* stream) {

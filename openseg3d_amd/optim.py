@@ -12,6 +12,10 @@ and rebuilt only when a pointer, a count or a hyper-parameter-set assignment cha
 ``zero_grad()``, redirected into the arena by ``dist.SceneParallel``); the hyper-parameters themselves travel in the
 kernel arguments.  The library's global optimizer post-step hook (ops._register_optimizer_hook) fires for these classes
 as for any torch optimizer, so packed and folded weights are rebuilt at their next use.
+
+``clip_grad_norm_`` / ``GradClipper`` / ``grad_norm`` (and ``optimizer.clip_grad_norm_``) clip the global L2 norm of the
+gradients between ``loss.backward()`` and ``step()`` on the same table design: three small launches beside the step, the
+norm accumulated in fp64.
 """
 import ctypes
 import math
@@ -146,6 +150,147 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
                     _lib.call("seg3d_optim_step_host", ctypes.c_void_p(plan.table.ctypes.data + offset * 64), n_rec, n_blocks,
                               hyper, n_sets, self._ALGO)
         return loss
+
+    def clip_grad_norm_(self, max_norm, error_if_nonfinite=False):
+        """``clip_grad_norm_`` over this optimizer's own ``param_groups``, between ``loss.backward()`` and ``step()``; the
+        clipper (record table, workspace) is kept on the optimizer.  Returns the total norm before clipping."""
+        clipper = self.__dict__.get("_clipper")
+        if clipper is None:
+            clipper = self.__dict__["_clipper"] = GradClipper([], max_norm)
+        clipper.params = [p for group in self.param_groups for p in group["params"]]
+        clipper.max_norm = _checked_max_norm(max_norm)
+        return clipper(error_if_nonfinite=error_if_nonfinite)
+
+
+def _checked_max_norm(max_norm):
+    max_norm = float(max_norm)
+    if not max_norm >= 0.0:
+        raise ValueError(f"max_norm must be >= 0, got {max_norm}")
+    return max_norm
+
+
+class _ClipPlan:
+    """The gradient table of a GradClipper, as last uploaded, and the workspace of its norm pass."""
+    __slots__ = ("sig", "dev", "table", "keep", "n", "blocks", "workspace", "workspace_bytes")
+
+
+class GradClipper:
+    """``torch.nn.utils.clip_grad_norm_`` (global L2 norm) on the library's table design (csrc/optim.hip):
+    the norm in two launches with the squares summed in fp64 (``seg3d_grad_norm``), the scale in one that returns at once
+    when the coefficient is 1 (``seg3d_grad_scale``).  ``clipper()`` clips in place and returns the total norm as a 0-d
+    float32 tensor on the parameters' device; ``clipper.last_coef`` is the coefficient that was applied,
+    min(max_norm / (norm + 1e-6), 1) in float32.  The table of (gradient pointer, count) records is kept across calls and
+    rebuilt only when one of them changes; a steady-state call makes no host synchronisation and allocates the 8-byte
+    result only.  CPU parameters run through the plain-C++ ``_host`` entries (the same definitions)."""
+
+    def __init__(self, parameters, max_norm, norm_type=2.0):
+        if isinstance(parameters, torch.Tensor):
+            parameters = [parameters]
+        if float(norm_type) != 2.0:
+            raise NotImplementedError(f"norm_type={norm_type!r} is not supported by openseg3d_amd.optim (the L2 norm only)")
+        self.params = list(parameters)
+        self.max_norm = _checked_max_norm(max_norm)
+        self.last_coef = None
+        self._plan = None
+
+    def __call__(self, error_if_nonfinite=False):
+        return self._run(self.max_norm, True, error_if_nonfinite)
+
+    def norm(self):
+        """The norm pass alone: no gradient is written."""
+        return self._run(math.inf, False, False)
+
+    @torch.no_grad()
+    def _run(self, max_norm, scale, error_if_nonfinite):
+        entries, dev = [], None
+        for p in self.params:
+            grad = p.grad
+            if grad is None:
+                continue
+            if p.dtype is not torch.float32 or grad.dtype is not torch.float32 or grad.is_sparse or not p.is_contiguous():
+                _MultiTensorOptimizer._refuse_tensor(p, grad)
+            if not grad.is_contiguous():
+                raise NotImplementedError("non-contiguous gradients are not supported by openseg3d_amd.optim.GradClipper")
+            if dev is None:
+                dev = grad.device
+                if dev.type not in ("cuda", "cpu"):
+                    raise NotImplementedError(f"parameters on device {dev} are not supported by openseg3d_amd.optim")
+            elif grad.device != dev:
+                raise NotImplementedError(f"openseg3d_amd.optim.GradClipper: all parameters must live on one device, got "
+                                          f"{dev} and {grad.device}")
+            if grad.numel():
+                entries.append((grad.data_ptr(), grad.numel()))
+        if dev is None:  # no parameter has a gradient: norm 0, nothing to launch
+            dev = self.params[0].device if self.params else torch.device("cpu")
+            self.last_coef = torch.ones((), dtype=torch.float32, device=dev)
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        cuda = dev.type == "cuda"
+        if cuda and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("openseg3d_amd.optim: gradient clipping under stream capture is not supported (the "
+                                      "record table follows the gradients' addresses from call to call)")
+        plan = self._plan
+        if plan is None or plan.sig != entries or plan.dev != dev:
+            plan = self._plan = _build_clip_plan(entries, dev, _block_elems())
+        if not cuda:
+            result = np.zeros((2,), np.float32)
+            args = (ctypes.c_void_p(plan.table.ctypes.data), plan.n, plan.blocks)
+            _lib.call("seg3d_grad_norm_host", *args, max_norm, ctypes.c_void_p(result.ctypes.data))
+            norm, coef = torch.tensor(result[0]), torch.tensor(result[1])
+            if error_if_nonfinite and not math.isfinite(float(result[0])):
+                raise RuntimeError(_NONFINITE)
+            if scale:
+                _lib.call("seg3d_grad_scale_host", *args, ctypes.c_void_p(result.ctypes.data + 4))
+                self.last_coef = coef
+            return norm
+        with torch.cuda.device(dev):
+            if ops._DEFERRED:  # weight gradients still pending on the side stream (a call from inside a backward pass)
+                ops.finish_deferred(dev)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            result = torch.empty((2,), dtype=torch.float32, device=dev)
+            args = (ctypes.c_void_p(plan.table.data_ptr()), plan.n, plan.blocks)
+            _lib.call("seg3d_grad_norm", *args, max_norm, ctypes.c_void_p(plan.workspace.data_ptr()), plan.workspace_bytes,
+                      ctypes.c_void_p(result.data_ptr()), stream)
+            if error_if_nonfinite and not math.isfinite(float(result[0])):  # the one read-back
+                raise RuntimeError(_NONFINITE)
+            if scale:
+                _lib.call("seg3d_grad_scale", *args, ctypes.c_void_p(result.data_ptr() + 4), stream)
+                self.last_coef = result[1]
+        return result[0]
+
+
+_NONFINITE = ("The total norm of order 2.0 for gradients from `parameters` is non-finite, so it cannot be clipped. To "
+              "disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+
+
+def _build_clip_plan(entries, dev, block):
+    plan = _ClipPlan()
+    plan.sig, plan.dev = list(entries), dev
+    rec = np.zeros((len(entries),), dtype=_RECORD)
+    blocks = 0
+    for i, (g, n) in enumerate(entries):
+        rec[i]["param"], rec[i]["count"], rec[i]["first_block"] = g, n, blocks
+        blocks += (n + block - 1) // block
+    plan.n, plan.blocks = len(entries), blocks
+    plan.workspace_bytes = _lib.query("seg3d_grad_norm_workspace_bytes", blocks)
+    if dev.type == "cuda":
+        plan.keep = torch.from_numpy(rec.view(np.uint8)).pin_memory()
+        plan.table = plan.keep.to(dev, non_blocking=True)
+        plan.workspace = torch.empty((max(plan.workspace_bytes, 8),), dtype=torch.uint8, device=dev)
+    else:
+        plan.keep, plan.table, plan.workspace = None, rec, None
+    return plan
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """``torch.nn.utils.clip_grad_norm_`` with the squares summed in fp64 on the device (a transient GradClipper; a training
+    loop keeps one, or calls the optimizer's ``clip_grad_norm_``).  ``foreach`` is accepted and ignored; with
+    ``error_if_nonfinite=True`` the norm is read back once, before any gradient is written."""
+    return GradClipper(parameters, max_norm, norm_type)(error_if_nonfinite=error_if_nonfinite)
+
+
+def grad_norm(parameters):
+    """The global L2 norm of the gradients (fp64 accumulation), nothing written: for logging."""
+    return GradClipper(parameters, math.inf).norm()
 
 
 def _block_elems(cache=[]):
