@@ -18,6 +18,18 @@
  *   - kernel offset k = (kz*3 + ky)*3 + kx, neighbour site = site + (kz-1, ky-1, kx-1).
  *
  * Each entry cites the reference interface (path:line under /root/reference) it replaces.
+ *
+ * This file is also the ONLY description of the ABI the Python binding has: openseg3d_amd/_lib.py parses it when the
+ * package is imported and derives every argtypes row, constant and ctypes.Structure from it, and refuses, naming the
+ * declaration, whatever falls outside this grammar (plain C; block and line comments are dropped first):
+ *   - #define SEG3D_<NAME> <decimal integer>, negative ones in parentheses: (-3);
+ *   - typedef struct { <fields> } seg3d_<name>;  a field is <type> <name>[, <name>...]; each name may carry one array
+ *     bound [<integer or SEG3D_ define>]; <type> is a scalar below, any pointer, or a struct typedef'd EARLIER;
+ *   - <return type> seg3d_<name>(<parameters>);  a parameter is a pointer (anything with a '*') or a scalar with an
+ *     optional name, or the list is `void`; no struct by value, no function pointer, no array parameter;
+ *   - scalars: int, int32_t, int64_t, uint64_t, size_t, float, double; the return type may also be const char*;
+ *   - the include guard, #include lines and every #ifdef __cplusplus ... #endif block are skipped; nothing else may
+ *     stand at file scope.
  */
 #ifndef SEG3D_HIP_H
 #define SEG3D_HIP_H
@@ -38,7 +50,9 @@ extern "C" {
 #define SEG3D_REDUCE_MEAN 1
 #define SEG3D_REDUCE_MAX 2
 
-/* ABI version; bumped whenever a signature below changes. */
+/* ABI version; bumped whenever a signature below changes.  seg3d_abi_version() returns the value the library was built
+ * with: a binding that read another one from this file is looking at a stale build. */
+#define SEG3D_ABI_VERSION 59
 int seg3d_abi_version(void);
 
 /* Text of the HIP runtime error behind the calling thread's most recent SEG3D_ELAUNCH
@@ -288,6 +302,16 @@ int seg3d_linear_wgrad_partials_bnrelu(const float* x_pre, const float* scale_in
                                        int64_t m, int32_t cin, int32_t cout, int32_t with_bias, void* workspace,
                                        size_t workspace_bytes, int32_t* chunks, void* stream);
 int seg3d_reduce_partials(const float* part, int32_t chunks, int64_t n, int64_t nw, float* dw, float* db, void* stream);
+/* One record of seg3d_reduce_partials_batched's `jobs`: a DEVICE array of n_jobs records sorted by first_block; job i
+ * covers blocks [first_block_i, first_block_{i+1}), ceil(n / 256) of them. */
+typedef struct {
+  const float* part;    /* [chunks][n] partial blocks */
+  float* dw;            /* [nw] */
+  float* db;            /* [n - nw], or NULL */
+  int64_t n, nw;
+  int32_t chunks, reserved;
+  int64_t first_block;
+} seg3d_reduce_job;     /* 56 bytes */
 int seg3d_reduce_partials_batched(const void* jobs, int32_t n_jobs, int64_t total_blocks, void* stream);
 /* a6  exact-fp32 variant for the per-point MLPs (segformer.py:21-32,58-76), whose split-bf16 forward error would land
  * directly on the logits: the same contract as seg3d_linear_* on v_mfma_f32_16x16x4_f32;

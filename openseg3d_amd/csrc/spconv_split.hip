@@ -85,27 +85,21 @@ __global__ __launch_bounds__(256) void pack_weight_split(const float* __restrict
 
 // One launch for many weights (all conv and Linear packs of a training step: the weights change every optimizer
 // step and every layer needs W and W^T).  jobs are sorted by first_block; a block finds its job by bisection.
-struct PackJob {
-    const float* src;
-    __bf16* dst;
-    int32_t cin_src, cout_src, kk, transpose, flip, reserved;
-    int64_t first_block;
-};
-static_assert(sizeof(PackJob) == 48, "PackJob layout is part of the C ABI (seg3d_pack_weights_batched)");
+static_assert(sizeof(seg3d_pack_job) == 48, "seg3d_pack_job layout is part of the C ABI (seg3d_pack_weights_batched)");
 
-__global__ __launch_bounds__(256) void pack_weights_batched(const PackJob* __restrict__ jobs, int n_jobs) {
+__global__ __launch_bounds__(256) void pack_weights_batched(const seg3d_pack_job* __restrict__ jobs, int n_jobs) {
     int lo = 0, hi = n_jobs - 1;
     while (lo < hi) {  // last job with first_block <= blockIdx.x
         const int mid = (lo + hi + 1) >> 1;
         if (jobs[mid].first_block <= (int64_t)blockIdx.x) lo = mid;
         else hi = mid - 1;
     }
-    const PackJob jb = jobs[lo];
-    const int cin_op = jb.transpose ? jb.cout_src : jb.cin_src;
-    const int cout_op = jb.transpose ? jb.cin_src : jb.cout_src;
+    const seg3d_pack_job jb = jobs[lo];
+    const int cin_op = jb.transpose ? jb.cout : jb.cin;
+    const int cout_op = jb.transpose ? jb.cin : jb.cout;
     const int64_t items = (int64_t)jb.kk * ((cin_op + 31) / 32) * (cout_op / 16) * 64;
     const int64_t t = ((int64_t)blockIdx.x - jb.first_block) * 256 + threadIdx.x;
-    if (t < items) pack_item(jb.src, jb.cin_src, jb.cout_src, jb.kk, jb.transpose, jb.flip, t, jb.dst);
+    if (t < items) pack_item(jb.src, jb.cin, jb.cout, jb.kk, jb.transpose, jb.flip, t, static_cast<__bf16*>(jb.dst));
 }
 
 // IO: storage of the activations.  0 = float32 in, float32 out (the default path); 3 = the same with a second float32
@@ -596,7 +590,7 @@ int seg3d_pack_weights_batched(const void* jobs, int32_t n_jobs, int64_t total_b
     if (n_jobs < 0 || total_blocks < 0 || total_blocks > 0x7FFFFFFF || (n_jobs > 0 && !jobs)) return SEG3D_EINVAL;
     if (n_jobs == 0 || total_blocks == 0) return SEG3D_OK;
     hipLaunchKernelGGL(pack_weights_batched, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
-                       static_cast<const PackJob*>(jobs), (int)n_jobs);
+                       static_cast<const seg3d_pack_job*>(jobs), (int)n_jobs);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }

@@ -291,24 +291,16 @@ __global__ __launch_bounds__(256) void wgrad_dense_reduce(const float* __restric
 
 // Many such reduces in ONE launch (all parameter-gradient partials of a backward pass whose join was deferred to the
 // pass's end: ~160 launches of 5-7 us each otherwise).  jobs are sorted by first_block; a block finds its job by bisection.
-struct ReduceJob {
-    const float* part;
-    float* dw;
-    float* db;
-    int64_t n, nw;
-    int32_t chunks, reserved;
-    int64_t first_block;
-};
-static_assert(sizeof(ReduceJob) == 56, "ReduceJob layout is part of the C ABI (seg3d_reduce_partials_batched)");
+static_assert(sizeof(seg3d_reduce_job) == 56, "seg3d_reduce_job layout is part of the C ABI (seg3d_reduce_partials_batched)");
 
-__global__ __launch_bounds__(256) void reduce_partials_batched(const ReduceJob* __restrict__ jobs, int n_jobs) {
+__global__ __launch_bounds__(256) void reduce_partials_batched(const seg3d_reduce_job* __restrict__ jobs, int n_jobs) {
     int lo = 0, hi = n_jobs - 1;
     while (lo < hi) {  // last job with first_block <= blockIdx.x
         const int mid = (lo + hi + 1) >> 1;
         if (jobs[mid].first_block <= (int64_t)blockIdx.x) lo = mid;
         else hi = mid - 1;
     }
-    const ReduceJob jb = jobs[lo];
+    const seg3d_reduce_job jb = jobs[lo];
     reduce_block(jb.part, jb.chunks, jb.n, jb.nw, jb.dw, jb.db, (int64_t)blockIdx.x - jb.first_block);
 }
 
@@ -403,7 +395,7 @@ extern "C" int seg3d_reduce_partials_batched(const void* jobs, int32_t n_jobs, i
     if (n_jobs < 0 || total_blocks < 0 || total_blocks > 0x7FFFFFFF || (n_jobs > 0 && !jobs)) return SEG3D_EINVAL;
     if (n_jobs == 0 || total_blocks == 0) return SEG3D_OK;
     hipLaunchKernelGGL(reduce_partials_batched, dim3((unsigned)total_blocks), dim3(256), 0, as_stream(stream),
-                       static_cast<const ReduceJob*>(jobs), (int)n_jobs);
+                       static_cast<const seg3d_reduce_job*>(jobs), (int)n_jobs);
     SEG3D_CHECK_LAUNCH();
     return SEG3D_OK;
 }

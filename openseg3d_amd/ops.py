@@ -219,13 +219,12 @@ def _state_for(fk):
     return key, st
 
 
-_REDUCE_JOB = None
+_REDUCE_JOB = np.dtype(_lib.struct("seg3d_reduce_job"))
 
 
 def _run_reduce_jobs(jobs, device, stream):
     """The queued partial-block sums (see _WgradFork.add_reduce) on `stream` (a torch stream; None = the current one): one
     launch each for up to two, otherwise ONE launch over a device job table (seg3d_reduce_partials_batched)."""
-    global _REDUCE_JOB
     if not jobs:
         return
     sp = _stream() if stream is None else ctypes.c_void_p(stream.cuda_stream)
@@ -235,10 +234,6 @@ def _run_reduce_jobs(jobs, device, stream):
         return
     import contextlib
     import numpy as np
-    if _REDUCE_JOB is None:
-        _REDUCE_JOB = np.dtype([("part", "<u8"), ("dw", "<u8"), ("db", "<u8"), ("n", "<i8"), ("nw", "<i8"), ("chunks", "<i4"),
-                                ("reserved", "<i4"), ("first_block", "<i8")])
-        assert _REDUCE_JOB.itemsize == 56
     rec = np.zeros((len(jobs),), dtype=_REDUCE_JOB)
     first = 0
     for i, (part, chunks, n, nw, dw, db, _) in enumerate(jobs):
@@ -763,9 +758,7 @@ def _refresh_packs(device):
     hit = _PACK_DESC.get(ident)
     if hit is None:
         import numpy as np
-        rec = np.zeros((len(stale),), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("cin", "<i4"), ("cout", "<i4"),
-                                                       ("kk", "<i4"), ("transpose", "<i4"), ("flip", "<i4"),
-                                                       ("reserved", "<i4"), ("first_block", "<i8")]))
+        rec = np.zeros((len(stale),), dtype=np.dtype(_lib.struct("seg3d_pack_job")))
         first = 0
         for i, (_, job, _) in enumerate(stale):
             rec[i] = (job.src_ptr, job.out.data_ptr(), job.cin, job.cout, job.kk, job.transpose, job.flip, 0, first)
@@ -2161,10 +2154,7 @@ if os.environ.get("SEG3D_KNN_LEVELS"):  # e.g. "0.1:2,0.5:3,3.0:4"
     KNN_GRID_LEVELS = tuple((float(a), int(b)) for a, b in (t.split(":") for t in os.environ["SEG3D_KNN_LEVELS"].split(",")))
 
 
-class _KnnLevel(ctypes.Structure):  # seg3d_knn_level
-    _fields_ = [("sorted_xyz", ctypes.c_void_p), ("src_index", ctypes.c_void_p), ("cell_end", ctypes.c_void_p),
-                ("table_keys", ctypes.c_void_p), ("table_vals", ctypes.c_void_p), ("capacity", ctypes.c_int64),
-                ("cell", ctypes.c_float), ("max_ring", ctypes.c_int32)]
+_KnnLevel = _lib.struct("seg3d_knn_level")
 
 
 def knn_query(nsample, xyz, new_xyz, offset, new_offset, levels=None):
@@ -2475,7 +2465,8 @@ def _class_weight_f32(class_weight, c, device, what):
     return w
 
 
-CE_MEAN_WEIGHTED, CE_MEAN_ALL, CE_THRESH, CE_RATIO = 0, 1, 2, 3  # SEG3D_CE_SELECT_* of include/seg3d_hip.h
+CE_MEAN_WEIGHTED, CE_MEAN_ALL = _lib.CE_SELECT_MEAN_WEIGHTED, _lib.CE_SELECT_MEAN_ALL
+CE_THRESH, CE_RATIO = _lib.CE_SELECT_THRESH, _lib.CE_SELECT_RATIO
 
 
 class _CrossEntropySelectFn(torch.autograd.Function):
@@ -2672,18 +2663,10 @@ def lovasz_softmax(logits, labels, ignore_index=255, classes="present", class_we
     return _LovaszSoftmaxFn.apply(logits, labels, ignore_index, mode, include, class_weight)
 
 
-CRITERION_MAX_HEADS = 4
-CRITERION_CE, CRITERION_LOVASZ = 1, 2
-_CRITERION_STATS_STRIDE = 68
-
-
-class CriterionHead(ctypes.Structure):
-    _fields_ = [("logits", ctypes.c_void_p), ("labels", ctypes.c_void_p), ("n", ctypes.c_int64), ("weight", ctypes.c_float)]
-
-
-class CriterionTable(ctypes.Structure):
-    """seg3d_criterion_table (include/seg3d_hip.h): up to four heads {logits, labels, n, head weight}."""
-    _fields_ = [("n_heads", ctypes.c_int32), ("heads", CriterionHead * CRITERION_MAX_HEADS)]
+CRITERION_MAX_HEADS, CRITERION_CE, CRITERION_LOVASZ = _lib.CRITERION_MAX_HEADS, _lib.CRITERION_CE, _lib.CRITERION_LOVASZ
+_CRITERION_STATS_STRIDE = _lib.CRITERION_STATS_STRIDE
+CriterionHead = _lib.struct("seg3d_criterion_head")
+CriterionTable = _lib.struct("seg3d_criterion_table")  # up to four heads {logits, labels, n, head weight}
 
 
 def criterion_table(logits, labels, head_weights):
@@ -2757,17 +2740,9 @@ def fused_criterion(logits, labels, head_weights, ignore_index=255, keep_thresh=
 
 
 # ------------------------------------------------------------------------------------------ evaluation (csrc/eval.hip)
-class TtaView(ctypes.Structure):
-    _fields_ = [("scale", ctypes.c_float), ("cos_a", ctypes.c_float), ("sin_a", ctypes.c_float),
-                ("flip_x", ctypes.c_int32), ("flip_y", ctypes.c_int32)]
-
-
-TTA_MAX_VIEWS = 64
-
-
-class TtaTable(ctypes.Structure):
-    """seg3d_tta_table (include/seg3d_hip.h): up to 64 views {scale, cos, sin, flip_x, flip_y}."""
-    _fields_ = [("n_views", ctypes.c_int32), ("batch_period", ctypes.c_int32), ("views", TtaView * TTA_MAX_VIEWS)]
+TTA_MAX_VIEWS = _lib.TTA_MAX_VIEWS
+TtaView = _lib.struct("seg3d_tta_view")
+TtaTable = _lib.struct("seg3d_tta_table")  # up to 64 views {scale, cos, sin, flip_x, flip_y}
 
 
 def tta_table(scales, angles, flip_x, flip_y, batch_period=0):
@@ -2863,16 +2838,8 @@ def argmax_confusion(scores=None, n_classes=None, pred_in=None, labels=None, his
 
 
 # ------------------------------------------------------------------------------------------ training augmentation (csrc/augment.hip)
-AUG_MAX_PASTE = 8
-
-
-class AugParams(ctypes.Structure):
-    """seg3d_aug_params (include/seg3d_hip.h): the per-row recipe of seg3d_aug_apply_f32."""
-    _fields_ = [("paste_cos", ctypes.c_double * AUG_MAX_PASTE), ("paste_sin", ctypes.c_double * AUG_MAX_PASTE),
-                ("offset", ctypes.c_double * 3), ("rot_cos", ctypes.c_float), ("rot_sin", ctypes.c_float),
-                ("scale", ctypes.c_float), ("n_paste", ctypes.c_int32), ("flip_x", ctypes.c_int32),
-                ("flip_y", ctypes.c_int32), ("global_on", ctypes.c_int32), ("batch_col", ctypes.c_int32),
-                ("batch_id", ctypes.c_float)]
+AUG_MAX_PASTE = _lib.AUG_MAX_PASTE
+AugParams = _lib.struct("seg3d_aug_params")  # the per-row recipe of seg3d_aug_apply_f32
 
 
 def aug_params(paste_angles=(), rot_angle=None, scale=1.0, offsets=(0.0, 0.0, 0.0), flip_x=False, flip_y=False,
@@ -3134,16 +3101,8 @@ def aug_gather_host(a, b, idx):
 
 
 # ------------------------------------------------------------------------------------------ instance copy-paste (csrc/augment_instance.hip)
-AUG_MAX_ANGLES = 20
-
-
-class AugInstancePlan(ctypes.Structure):
-    """seg3d_aug_instance_plan (include/seg3d_hip.h): one instance to paste and every number drawn for it."""
-    _fields_ = [("row_begin", ctypes.c_int64), ("n_rows", ctypes.c_int32), ("label", ctypes.c_int32),
-                ("height", ctypes.c_double), ("loc_noise", ctypes.c_double * 3), ("rot_cos", ctypes.c_double),
-                ("rot_sin", ctypes.c_double), ("local_on", ctypes.c_int32), ("flip", ctypes.c_int32),
-                ("n_angles", ctypes.c_int32), ("reserved", ctypes.c_int32), ("ang_cos", ctypes.c_double * AUG_MAX_ANGLES),
-                ("ang_sin", ctypes.c_double * AUG_MAX_ANGLES)]
+AUG_MAX_ANGLES = _lib.AUG_MAX_ANGLES
+AugInstancePlan = _lib.struct("seg3d_aug_instance_plan")  # one instance to paste and every number drawn for it
 
 
 def aug_instance_plan(row_begin, n_rows, label, height, loc_noise=None, rot_noise=None, flip=False, angles=()):
@@ -3218,14 +3177,8 @@ def aug_instance_paste_host(points, labels, ground_ids, bank, plans, cap_add=Non
 
 
 # ------------------------------------------------------------------------------------------ instance bank extraction (csrc/instance_extract.hip)
-class InstanceCluster(ctypes.Structure):
-    """seg3d_instance_cluster (include/seg3d_hip.h): 56 bytes, seven 8-byte words."""
-    _fields_ = [("label", ctypes.c_int32), ("begin", ctypes.c_int32), ("rows", ctypes.c_int32), ("kept", ctypes.c_int32),
-                ("center", ctypes.c_double * 3), ("radius", ctypes.c_double), ("height", ctypes.c_double)]
-
-
-INSTANCE_CLUSTER_DTYPE = np.dtype([("label", np.int32), ("begin", np.int32), ("rows", np.int32), ("kept", np.int32),
-                                   ("center", np.float64, (3,)), ("radius", np.float64), ("height", np.float64)])
+InstanceCluster = _lib.struct("seg3d_instance_cluster")  # 56 bytes, seven 8-byte words
+INSTANCE_CLUSTER_DTYPE = np.dtype(InstanceCluster)
 INSTANCE_EXTRACT_CAP = 1024  # the wrappers' first guess of cap_clusters; a frame with more is run once more
 
 
@@ -3288,19 +3241,10 @@ def instance_extract_host(points, labels, target_ids, min_points, ground_ids, ep
 
 
 # ------------------------------------------------------------------------------------------ frame assembly (csrc/frame.hip)
-FRAME_MAX_SWEEPS = 8
-
-
-class Sweep(ctypes.Structure):
-    """seg3d_sweep (include/seg3d_hip.h)."""
-    _fields_ = [("rows", ctypes.c_void_p), ("n_rows", ctypes.c_int64), ("stride", ctypes.c_int64),
-                ("matrix", ctypes.c_double * 12), ("lag", ctypes.c_double), ("transform", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
-
-
-class SweepTable(ctypes.Structure):
-    """seg3d_sweep_table: up to 8 sweeps of one frame; ``arrays`` keeps the rows alive, ``dim`` / ``dtype`` describe them."""
-    _fields_ = [("n_sweeps", ctypes.c_int32), ("reserved", ctypes.c_int32), ("sweeps", Sweep * FRAME_MAX_SWEEPS)]
+FRAME_MAX_SWEEPS = _lib.FRAME_MAX_SWEEPS
+Sweep = _lib.struct("seg3d_sweep")
+# up to 8 sweeps of one frame; sweep_table() adds ``arrays``, which keeps the rows alive, and ``dim`` / ``dtype``, which describe them
+SweepTable = _lib.struct("seg3d_sweep_table")
 
 
 def sweep_table(sweeps, matrices=None, lags=None, dim=None):
@@ -3440,20 +3384,10 @@ def range_image_labels_host(pred, points_ri, n_classes, rows=RANGE_IMAGE_SHAPE[0
 
 
 # ------------------------------------------------------------------------------------------ image features (csrc/image_features.hip)
-IMAGE_MAX_CAMERAS = 8
+IMAGE_MAX_CAMERAS = _lib.IMAGE_MAX_CAMERAS
 IMAGE_MAX_CHANNELS = 64
-
-
-class FeatureMap(ctypes.Structure):
-    """seg3d_feature_map (include/seg3d_hip.h)."""
-    _fields_ = [("data", ctypes.c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
-                ("channel_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("col_stride", ctypes.c_int64)]
-
-
-class FeatureMapTable(ctypes.Structure):
-    """seg3d_feature_map_table: up to 8 cameras; ``arrays`` keeps the maps alive."""
-    _fields_ = [("n_maps", ctypes.c_int32), ("channels", ctypes.c_int32), ("elem_bytes", ctypes.c_int32),
-                ("reserved", ctypes.c_int32), ("maps", FeatureMap * IMAGE_MAX_CAMERAS)]
+FeatureMap = _lib.struct("seg3d_feature_map")
+FeatureMapTable = _lib.struct("seg3d_feature_map_table")  # up to 8 cameras; feature_map_table() adds ``arrays``, which keeps the maps alive
 
 
 class ImageFeatureIndexError(IndexError, _lib.Seg3dError):

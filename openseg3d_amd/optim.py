@@ -27,10 +27,7 @@ from torch.optim.lr_scheduler import CosineAnnealingLR, LRScheduler, OneCycleLR
 from . import _lib
 from . import ops  # noqa: F401  (registers the weight-cache hook on every optimizer step)
 
-# seg3d_optim_tensor of include/seg3d_hip.h
-_RECORD = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state0", "<u8"), ("state1", "<u8"), ("count", "<i8"),
-                    ("first_block", "<i8"), ("hyper", "<i4"), ("flags", "<i4"), ("reserved", "<i8")])
-assert _RECORD.itemsize == 64
+_RECORD = np.dtype(_lib.struct("seg3d_optim_tensor"))
 
 
 def sgd_scalars(lr, weight_decay, momentum):
