@@ -338,12 +338,12 @@ def compute_loss(pred_result, data_dict, criterion, cfg):
     """tools/train.py:71-110: criterion on the point logits, the voxel logits and (x MODEL.AUX_LOSS_WEIGHT) the
     stride-8 auxiliary logits, whose ground truth is looked up by nearest fine voxel centre (ops.aux_voxel_labels)."""
     # The auxiliary labels (a kNN lookup: no gradient, independent of the other two heads) come from the planned index
-    # of the batch (Segformer.prepare_batch) where there is one: a gather.  Otherwise they are looked up on the second
+    # of the batch (Segmentor.prepare_batch, both segmentors) where there is one: a gather.  Otherwise they are looked up on the second
     # stream while this one computes the point and voxel losses; the streams meet in front of the auxiliary loss.
     aux_gt = side = None
     if "aux_voxel_out" in pred_result:
         dev = pred_result["aux_voxel_out"].device
-        planned = (pred_result.get("index_plan") or {}).get("aux_label_index")  # Segformer.forward of a planned batch
+        planned = (pred_result.get("index_plan") or {}).get("aux_label_index")  # either segmentor's forward of a planned batch
         overlap = AUX_OVERLAP and dev.type == "cuda" and planned is None
         if overlap:
             main, side = torch.cuda.current_stream(dev), ops.side_stream(dev)

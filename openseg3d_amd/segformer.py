@@ -5,6 +5,9 @@ Host-side mirror of the reference's default model (``cfg.MODEL.SEGMENTOR == 'seg
   seg3d/models/voxel_encoders/vfe.py, seg3d/models/layers/se_layer.py.
 Same constructor arguments, same ``forward(batch_dict) -> OrderedDict`` contract and the same
 state_dict keys / shapes (tests/golden/segformer_keys.json), so reference checkpoints load.
+The model layer of both segmentors lives here once: SparseBasicBlock, UpBlock and the Segmentor base class (construction
+of everything around the backbone, weight initialization, prepare_batch, forward).  Segformer adds its PointTransformer,
+spnet.SPNet its SparseUnet.
 
 What runs where: voxel-feature reduce, every sparse convolution, window partition + attention, every Linear /
 LayerNorm / BatchNorm(+ReLU) pass with MFMA-sized channels, the voxel->point gather, kNN and the training criterion run
@@ -153,7 +156,11 @@ def _block_tail(block, y, x):
 
 
 class SparseBasicBlock(spconv.SparseModule):
-    def __init__(self, inplanes, planes, norm_fn, act_fn, indice_key=None, with_se=False, with_sa=False):
+    """conv-BN-ReLU-conv-BN (+ squeeze-excite over each sample's voxels, + spatial attention) + identity, ReLU: the block of
+    both backbones (pointtransformer.py:13-66, spconv_unet.py:12-66).  The two reference classes order ``indice_key`` and
+    ``with_se`` differently, so the options are keyword-only here."""
+
+    def __init__(self, inplanes, planes, norm_fn, act_fn, *, indice_key=None, with_se=False, with_sa=False):
         super().__init__()
         self.conv1 = spconv.SubMConv3d(inplanes, planes, 3, padding=1, bias=True, indice_key=indice_key)
         self.bn1 = norm_fn(planes)
@@ -165,7 +172,12 @@ class SparseBasicBlock(spconv.SparseModule):
 
     def forward(self, x):
         plain = self.se is None and self.sa is None
-        if self.conv1.fusable_with(self.bn1, x) and self.conv2.fusable_with(self.bn2, x):  # inference: two launches
+        # A block with squeeze-excite and no spatial attention keeps the separate conv -> BatchNorm passes in inference:
+        # SparseUnet's conv3 / conv4 tails run that way, and folding them changes SPNet's inference bits -- a change of its
+        # own, with its own measurement.
+        se_only = self.se is not None and self.sa is None
+        if not se_only and self.conv1.fusable_with(self.bn1, x) and self.conv2.fusable_with(self.bn2, x):
+            # inference: BatchNorm folded into the packed weights, two launches
             y = self.conv1.forward_bn_act(x, self.bn1, relu=True)
             if plain:
                 return self.conv2.forward_bn_act(y, self.bn2, relu=True, res=x.features)
@@ -240,18 +252,15 @@ class PointTransformer(nn.Module):
         level = spconv.SiteLevel(batch_dict["voxel_coords"].int(), self.sparse_shape, batch_dict["batch_size"])
         batch_dict["site_level"] = level
         widths = (48, 96, 192, 384)
-        level.seed_chain(3)  # sites of the three strided levels: chained on the device, one read-back
         launched = []
-        for k in range(4):
-            level.subm()
-            level.subm_plan()
+
+        def window_plan(k, level):
             part = getattr(self, f"swformer_block{k + 1}")[0]
             if part not in level.window_plans:  # partition kernels queued now, counts of all stages read back once below
                 level.window_plans[part] = part.launch_plan(level.coords, level.batch_size, widths[k])
                 launched.append(level.window_plans[part])
-            if k < 3:
-                level.parity_order()
-                level = level.down()[0]
+
+        level.plan_chain(3, window_plan)
         if launched:
             SparseWindowPartitionLayer.finish_plans(launched)
         return batch_dict
@@ -343,7 +352,7 @@ class DeepFusionBlock(nn.Module):
 
     def neighbours(self, points, point_id_offset):
         """int32 [N, k] rows of the k nearest current-sweep points (deep_fusion.py:31).  Depends on the points alone: the
-        batch builder / input pipeline may compute it ahead of the forward (Segformer.prepare_batch)."""
+        batch builder / input pipeline may compute it ahead of the forward (Segmentor.prepare_batch)."""
         xyz = points.contiguous() if self.faithful_stride else points[:, :3].contiguous()
         knn_ids, _ = ops.knn_query(self.n_neighbors, xyz, xyz, point_id_offset, point_id_offset)
         return knn_ids
@@ -370,8 +379,15 @@ class DeepFusionBlock(nn.Module):
         return self.c_proj((attn.unsqueeze(-1) * v[knn_ids]).sum(dim=1))
 
 
-class Segformer(nn.Module):
-    def __init__(self, dataset, batching_info, window_shape, depths, drop_path_rate):
+class Segmentor(nn.Module):
+    """What Segformer and SPNet share (seg3d/models/segmentors/segformer.py:12-146, spnet.py:12-148): point MLP -> VFE ->
+    backbone -> voxel-to-point gather -> (image fusion) -> fusion MLP -> squeeze-excite -> classifier, the weight
+    initialization and the index plan a batch can carry.  A subclass names its backbone and builds it."""
+
+    backbone_name = None  # the attribute (and state_dict prefix) the backbone is registered under
+    voxel_feature_channel = None  # the backbone's output channels
+
+    def __init__(self, dataset, **backbone_args):
         super().__init__()
         dim_point = dataset.dim_point + (2 if dataset.use_cylinder else 0)
         self.use_multi_sweeps = bool(dataset.use_multi_sweeps)
@@ -381,12 +397,9 @@ class Segformer(nn.Module):
                                      last_plain=True)
         # multi-sweep: the voxel features are the MEAN of the raw rows of all sweeps (segformer.py:34-37,105-107)
         self.vfe = VFE(dim_point, reduce="mean") if self.use_multi_sweeps else VFE(self.point_feature_channel, "max")
-        self.scatter = VFE(3, reduce="mean")  # present (and unused) in the reference: segformer.py:39
-        self.voxel_feature_channel = 32
-        self.point_transformer = PointTransformer(
-            self.vfe.voxel_feature_channel, self.voxel_feature_channel, dataset.grid_size, dataset.voxel_size,
-            dataset.point_cloud_range, batching_info=batching_info, window_shape=window_shape, depths=depths,
-            drop_path_rate=drop_path_rate, num_classes=dataset.num_classes)
+        # registered here, between vfe and deep_fusion: the order fixes the state_dict's key order and the order in which
+        # construction and weight_initialization consume the torch generator
+        setattr(self, self.backbone_name, self.build_backbone(dataset, **backbone_args))
         self.image_feature_channel = dataset.dim_image_feature if self.use_image_feature else 0
         if self.use_image_feature:
             self.deep_fusion = DeepFusionBlock(self.point_feature_channel + self.voxel_feature_channel,
@@ -400,8 +413,17 @@ class Segformer(nn.Module):
                                    RowLinear(64, dataset.num_classes, bias=False))
         self.weight_initialization()
 
+    def build_backbone(self, dataset, **backbone_args):
+        """The voxel backbone, on ``self.vfe.voxel_feature_channel`` input and ``self.voxel_feature_channel`` output
+        channels: a module with ``prepare(batch_dict)``, ``forward(batch_dict)``, ``voxel_size`` and ``point_cloud_range``."""
+        raise NotImplementedError
+
+    @property
+    def backbone(self):
+        return getattr(self, self.backbone_name)
+
     def weight_initialization(self):
-        """segformer.py:78-92: kaiming-normal Linear weights, unit norms; sparse convs keep their default init."""
+        """segformer.py:78-92, spnet.py:77-92: kaiming-normal Linear weights, unit norms; sparse convs keep their default init."""
         for m in self.modules():
             if isinstance(m, nn.Linear):
                 nn.init.kaiming_normal_(m.weight)
@@ -416,7 +438,7 @@ class Segformer(nn.Module):
         coordinates only, and all of the forward's host read-backs), built ahead of time and carried by the batch -- an
         input pipeline calls this for batch i+1 on its own stream while batch i trains (bench.py)."""
         if "site_level" not in batch_dict:
-            self.point_transformer.prepare(batch_dict)
+            self.backbone.prepare(batch_dict)
         if self.use_image_feature and "fusion_knn" not in batch_dict:
             # DeepFusionBlock's neighbour search reads the points only (13 ms of a 63 ms multi-sweep forward): part of the plan
             cur_points, _ = self._current_sweep(batch_dict)
@@ -434,9 +456,8 @@ class Segformer(nn.Module):
         fine = coarse = batch_dict["site_level"]
         for _ in range(3):
             coarse = coarse.down()[0]
-        pt = self.point_transformer
-        return ops.aux_voxel_label_index(fine.coords, coarse.coords, batch_dict["batch_size"], pt.voxel_size,
-                                         pt.point_cloud_range)
+        return ops.aux_voxel_label_index(fine.coords, coarse.coords, batch_dict["batch_size"], self.backbone.voxel_size,
+                                         self.backbone.point_cloud_range)
 
     def _current_sweep(self, batch_dict):
         """(rows of the current sweep without the batch column, their row numbers or None) -- segformer.py:96-100; the row
@@ -465,7 +486,7 @@ class Segformer(nn.Module):
             seg = ops.SegmentIndex(ids, n_voxels)
         if PLAN_FIRST and "site_level" not in batch_dict:  # (a batch may arrive with its plan: prepare_batch below)
             # (Running the plan on a second stream under the point encoder changed nothing: 48.4 vs 48.5 ms.)
-            self.point_transformer.prepare(batch_dict)
+            self.backbone.prepare(batch_dict)
 
         if self.use_multi_sweeps:
             cur_points, cur_rows = self._current_sweep(batch_dict)  # rows whose time lag column == 0 (segformer.py:98)
@@ -489,7 +510,7 @@ class Segformer(nn.Module):
         point_features = self.point_encoder(cur_points)
 
         batch_dict["voxel_features"] = self.vfe(points if self.use_multi_sweeps else point_features, seg)
-        batch_dict = self.point_transformer(batch_dict)
+        batch_dict = self.backbone(batch_dict)
 
         point_voxel_features = ops.gather_rows(batch_dict["voxel_features"], cur_ids, cur_seg)
         fused = torch.cat([point_features, point_voxel_features], dim=1)
@@ -519,6 +540,22 @@ class Segformer(nn.Module):
             # it is plan material and not one of the forward's output tensors
             result["index_plan"] = {"aux_label_index": batch_dict["aux_label_index"]}
         return result
+
+
+class Segformer(Segmentor):
+    backbone_name, voxel_feature_channel = "point_transformer", 32
+
+    def __init__(self, dataset, batching_info, window_shape, depths, drop_path_rate):
+        super().__init__(dataset, batching_info=batching_info, window_shape=window_shape, depths=depths,
+                         drop_path_rate=drop_path_rate)
+
+    def build_backbone(self, dataset, **backbone_args):
+        # present (and unused) in the reference, segformer.py:39.  Assigned here, not in __init__, because the base class calls
+        # this method between vfe and the backbone: that is where `scatter` stands in the registration order
+        self.scatter = VFE(3, reduce="mean")
+        return PointTransformer(self.vfe.voxel_feature_channel, self.voxel_feature_channel, dataset.grid_size,
+                                dataset.voxel_size, dataset.point_cloud_range, num_classes=dataset.num_classes,
+                                **backbone_args)
 
 
 def build_segmentor(cfg, dataset):

@@ -117,6 +117,21 @@ class SiteLevel:
             self._coarse = None
         return self._down
 
+    def plan_chain(self, levels, per_level):
+        """Everything a U-shaped backbone derives from the sites of this level and of the ``levels`` strided ones below it,
+        queued before any feature kernel: the strided site lists (chained on the device, one read-back), per level the
+        submanifold table and its tile plan, the model's own extra (``per_level(k, level)``), and the parity order of every
+        level that is stepped down from."""
+        level = self
+        level.seed_chain(levels)
+        for k in range(levels + 1):
+            level.subm()
+            level.subm_plan()
+            per_level(k, level)
+            if k < levels:
+                level.parity_order()
+                level = level.down()[0]
+
 
 class SparseConvTensor:
     def __init__(self, features, indices, spatial_shape, batch_size, _level=None, _indice_dict=None):

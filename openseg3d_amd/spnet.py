@@ -5,11 +5,12 @@
   seg3d/models/layers/ocr.py:10-116               SpatialGatherModule, ObjectAttentionBlock, OCRLayer
 
 Same constructor arguments, ``forward(batch_dict) -> OrderedDict`` contract and state_dict keys / shapes as the
-reference (tests/golden/spnet_keys.json).  Every sparse convolution, BatchNorm(+ReLU) pass, voxel reduce and
-voxel->point gather runs in libseg3d_hip.so exactly as in Segformer; the object-context attention works on
+reference (tests/golden/spnet_keys.json).  This file holds what only SPNet has: the object-context layers and the
+SparseUnet backbone.  SparseBasicBlock, UpBlock and everything around the backbone (segformer.Segmentor: construction,
+prepare_batch, forward) are Segformer's own objects, so every sparse convolution, BatchNorm(+ReLU) pass, voxel reduce
+and voxel->point gather runs in libseg3d_hip.so exactly as there; the object-context attention works on
 [voxels of the stride-8 level] x [22 class proxies] matrices and stays on torch.
 """
-from collections import OrderedDict
 from functools import partial
 
 import torch
@@ -17,46 +18,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from . import segformer as segformer_mod
 from . import spconv
-from .segformer import (ConvBnAct, DeepFusionBlock, FlattenSELayer, FusedMLP, RowLinear, SALayer, UpBlock, VFE, _block_tail,
-                        _bn_mlp, conv_module)
-
-
-class SparseBasicBlock(spconv.SparseModule):
-    """conv-BN-ReLU-conv-BN (+ squeeze-excite over each sample's voxels, + spatial attention) + identity, ReLU
-    (spconv_unet.py:12-66)."""
-
-    def __init__(self, inplanes, planes, norm_fn, act_fn, with_se=False, indice_key=None, with_sa=False):
-        super().__init__()
-        self.conv1 = spconv.SubMConv3d(inplanes, planes, 3, padding=1, bias=True, indice_key=indice_key)
-        self.bn1 = norm_fn(planes)
-        self.act = act_fn
-        self.conv2 = spconv.SubMConv3d(planes, planes, 3, padding=1, bias=True, indice_key=indice_key)
-        self.bn2 = norm_fn(planes)
-        self.se = FlattenSELayer(planes) if with_se else None
-        self.sa = SALayer(planes, indice_key=indice_key) if with_sa else None  # (the reference's SparseUnet never sets it)
-
-    def forward(self, x):
-        if self.sa is not None:
-            if self.conv1.fusable_with(self.bn1, x) and self.conv2.fusable_with(self.bn2, x):  # inference, BatchNorm folded
-                y = self.conv1.forward_bn_act(x, self.bn1, relu=True)
-                return _block_tail(self, self.conv2.forward_bn_act(y, self.bn2, relu=False, res=None), x)
-            y = self.conv1(x)
-            y = y.replace_feature(ops.batch_norm_act(y.features, self.bn1, relu=True))
-            y = self.conv2(y)
-            return _block_tail(self, y.replace_feature(ops.batch_norm_act(y.features, self.bn2, relu=False)), x)
-        if self.se is None and self.conv1.fusable_with(self.bn1, x) and self.conv2.fusable_with(self.bn2, x):
-            y = self.conv1.forward_bn_act(x, self.bn1, relu=True)  # inference: BatchNorm folded, two launches
-            return self.conv2.forward_bn_act(y, self.bn2, relu=True, res=x.features)
-        y = self.conv1(x)
-        y = y.replace_feature(ops.batch_norm_act(y.features, self.bn1, relu=True))
-        y = self.conv2(y)
-        if self.se is None:
-            return y.replace_feature(ops.batch_norm_act(y.features, self.bn2, relu=True, res=x.features))
-        f = ops.batch_norm_act(y.features, self.bn2, relu=False)
-        f = self.se(f, y.indices[:, 0], y.level.sample_offsets())
-        return y.replace_feature(torch.relu(f + x.features))
+from .segformer import (ConvBnAct, FusedMLP, RowLinear, SALayer, Segmentor, SparseBasicBlock, UpBlock,  # SALayer: re-exported
+                        conv_module)
 
 
 class SpatialGatherModule(nn.Module):
@@ -158,7 +122,16 @@ class SparseUnet(nn.Module):
         self.conv4 = spconv.SparseSequential(
             conv_module(128, 256, norm_fn, act_fn, "spconv", "spconv4"), block(256, 256, indice_key="subm4"),
             block(256, 256, indice_key="subm4"), block(256, 256, with_se=True, indice_key="subm4"))
-        up = partial(_UpBlock, norm_fn=norm_fn, act_fn=act_fn)
+
+        def up(inplanes, planes, conv_type, layer_id):
+            # The lateral transform's conv weights are drawn a second time, behind the block's other convs: the order in which
+            # this backbone has always consumed the torch generator (it used to build each transform twice).  It keeps the
+            # weights a seed gives, the benchmark's and the tests' among them, what they were.
+            blk = UpBlock(inplanes, planes, norm_fn, act_fn, conv_type, layer_id)
+            blk.transform.conv1.reset_parameters()
+            blk.transform.conv2.reset_parameters()
+            return blk
+
         self.up4 = up(256, 128, conv_type="inverseconv", layer_id=4)
         self.up3 = up(128, 64, conv_type="inverseconv", layer_id=3)
         self.up2 = up(64, 32, conv_type="inverseconv", layer_id=2)
@@ -174,15 +147,8 @@ class SparseUnet(nn.Module):
         segformer.PointTransformer.prepare)."""
         level = spconv.SiteLevel(batch_dict["voxel_coords"].int(), self.sparse_shape, batch_dict["batch_size"])
         batch_dict["site_level"] = level
-        level.seed_chain(3)
-        for k in range(4):
-            level.subm()
-            level.subm_plan()
-            if k >= 2:
-                level.sample_offsets()  # squeeze-excite of conv3 / conv4, OCR
-            if k < 3:
-                level.parity_order()
-                level = level.down()[0]
+        # per-sample row offsets of levels 2 and 3: squeeze-excite of conv3 / conv4, OCR
+        level.plan_chain(3, lambda k, level: level.sample_offsets() if k >= 2 else None)
         return batch_dict
 
     def forward(self, batch_dict):
@@ -207,99 +173,9 @@ class SparseUnet(nn.Module):
         return batch_dict
 
 
-class _UpBlock(UpBlock):
-    """UpBlock whose lateral transform is this file's SparseBasicBlock (same parameters; spconv_unet.py:69-112)."""
+class SPNet(Segmentor):
+    backbone_name, voxel_feature_channel = "voxel_encoder", 64
 
-    def __init__(self, inplanes, planes, norm_fn, act_fn, conv_type, layer_id):
-        super().__init__(inplanes, planes, norm_fn, act_fn, conv_type, layer_id)
-        self.transform = SparseBasicBlock(inplanes, inplanes, norm_fn, act_fn, indice_key=f"subm{layer_id}")
-
-
-class SPNet(nn.Module):
-    def __init__(self, dataset):
-        super().__init__()
-        dim_point = dataset.dim_point + (2 if dataset.use_cylinder else 0)
-        self.use_multi_sweeps = bool(dataset.use_multi_sweeps)
-        self.use_image_feature = bool(dataset.use_image_feature)
-        self.point_feature_channel = 64
-        self.point_encoder = _bn_mlp([dim_point, 64, 128, 256, self.point_feature_channel], first_bn=dim_point,
-                                     last_plain=True)
-        self.vfe = VFE(dim_point, reduce="mean") if self.use_multi_sweeps else VFE(self.point_feature_channel, "max")
-        self.voxel_feature_channel = 64
-        self.voxel_encoder = SparseUnet(self.vfe.voxel_feature_channel, self.voxel_feature_channel, dataset.grid_size,
-                                        dataset.voxel_size, dataset.point_cloud_range, dataset.num_classes)
-        self.image_feature_channel = dataset.dim_image_feature if self.use_image_feature else 0
-        if self.use_image_feature:
-            self.deep_fusion = DeepFusionBlock(self.point_feature_channel + self.voxel_feature_channel,
-                                               self.image_feature_channel, 32, 16)
-        self.fusion_feature_channel = 64
-        self.fusion_encoder = _bn_mlp([self.point_feature_channel + self.voxel_feature_channel
-                                       + self.image_feature_channel, 256, 128, self.fusion_feature_channel])
-        self.se = FlattenSELayer(self.fusion_feature_channel)
-        self.classifier = FusedMLP(RowLinear(self.fusion_feature_channel, 64, bias=False), nn.BatchNorm1d(64),
-                                   nn.ReLU(True), nn.Dropout(0.3), RowLinear(64, dataset.num_classes, bias=False))
-        self.weight_initialization()
-
-    def weight_initialization(self):
-        """spnet.py:77-92."""
-        for m in self.modules():
-            if isinstance(m, nn.Linear):
-                nn.init.kaiming_normal_(m.weight)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, (nn.BatchNorm1d, nn.LayerNorm)):
-                nn.init.constant_(m.weight, 1.0)
-                nn.init.constant_(m.bias, 0)
-
-    def prepare_batch(self, batch_dict):
-        """The forward's index plan, built ahead of time and carried by the batch (segformer.Segformer.prepare_batch)."""
-        if "site_level" not in batch_dict:
-            self.voxel_encoder.prepare(batch_dict)
-        return batch_dict
-
-    def forward(self, batch_dict):
-        if self.training and torch.is_grad_enabled():
-            ops.probe_deferred_join(batch_dict["points"].device)  # once per process: self-test of the deferred join
-        with ops.deferred_bn_counters():  # one launch for all BatchNorm step counters
-            return self._forward(batch_dict)
-
-    def _forward(self, batch_dict):
-        points = batch_dict["points"][:, 1:]
-        ids = batch_dict["point_voxel_ids"]
-        n_voxels = batch_dict["voxel_coords"].shape[0]
-        seg = batch_dict.get("point_voxel_index")
-        if seg is None:
-            seg = ops.SegmentIndex(ids, n_voxels)
-        if segformer_mod.PLAN_FIRST and "site_level" not in batch_dict:
-            self.voxel_encoder.prepare(batch_dict)
-        if self.use_multi_sweeps:
-            cur_rows = batch_dict.get("cur_rows")  # found by the batch's builder (MultiScaleFlipAug), else here
-            if cur_rows is None:
-                cur_rows = torch.nonzero(points[:, 3] == 0).view(-1)  # spnet.py:97
-            cur_points, cur_ids, cur_seg = points[cur_rows], seg.ids[cur_rows], None
-            batch_rows = batch_dict["points"][cur_rows, 0]
-        else:
-            cur_points, cur_ids, cur_seg, batch_rows = points, seg.ids, seg, batch_dict["points"][:, 0]
-        point_features = self.point_encoder(cur_points)
-        batch_dict["voxel_features"] = self.vfe(points if self.use_multi_sweeps else point_features, seg)
-        batch_dict = self.voxel_encoder(batch_dict)
-
-        point_voxel_features = ops.gather_rows(batch_dict["voxel_features"], cur_ids, cur_seg)
-        fused = torch.cat([point_features, point_voxel_features], dim=1)
-        if self.use_image_feature:
-            img = self.deep_fusion(cur_points, batch_dict["point_id_offset"].int(), fused,
-                                   batch_dict["point_image_features"], batch_dict.get("fusion_knn"))
-            fused = torch.cat([fused, img], dim=1)
-        fused = self.fusion_encoder(fused)
-        row_offsets = batch_dict.get("point_row_offsets")
-        if row_offsets is None and batch_dict.get("point_id_offset") is not None:
-            row_offsets = [int(v) for v in batch_dict["point_id_offset"].tolist()]
-        fused = fused + self.se(fused, batch_rows, row_offsets)
-
-        result = OrderedDict()
-        result["point_out"] = self.classifier(fused)
-        result["voxel_out"] = batch_dict["voxel_out"]
-        result["aux_voxel_out"] = batch_dict["aux_voxel_out"]
-        result["voxel_coords"] = batch_dict["voxel_coords"]
-        result["aux_voxel_coords"] = batch_dict["aux_voxel_coords"]
-        return result
+    def build_backbone(self, dataset):
+        return SparseUnet(self.vfe.voxel_feature_channel, self.voxel_feature_channel, dataset.grid_size,
+                          dataset.voxel_size, dataset.point_cloud_range, dataset.num_classes)

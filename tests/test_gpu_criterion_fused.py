@@ -148,12 +148,14 @@ def test_fused_matches_oracle(dev, shape, variant):
         assert err <= 1e-9 + 2e-4 * top, (h, err)
 
 
-def test_model_path_planned_index_and_switch(dev):
-    """On a real forward: the index prepare_batch plans is the one ops.aux_voxel_labels looks up and survives copies of the
-    result (dict(), the data-parallel wrapper's rebuild); compute_loss gives the same float with and without it and with
-    FUSED_CRITERION on and off; every parameter gradient is equal."""
+@pytest.mark.parametrize("segmentor", ["segformer", "spnet"])
+def test_model_path_planned_index_and_switch(dev, segmentor):
+    """On a real forward of either segmentor: the index prepare_batch plans is the one ops.aux_voxel_labels looks up and
+    survives copies of the result (dict(), the data-parallel wrapper's rebuild); compute_loss gives the same float with and
+    without it and with FUSED_CRITERION on and off; every parameter gradient is equal."""
     from openseg3d_amd import batch as B, config, dist, losses, ops, scene, segformer
     cfg = config.default_cfg()
+    cfg.MODEL.SEGMENTOR = segmentor
     ds = config.DatasetSpec(cfg)
     torch.manual_seed(0)
     model = segformer.build_segmentor(cfg, ds).to(dev).train()

@@ -1,7 +1,8 @@
 """The one-channel submanifold conv and the fused SALayer gate on the device (csrc/sa_gate.hip): bit for bit against
 the library's host twins wherever no expf is involved (the logits; dx, dw and dbias of the plain conv, whose ds is the
 incoming gradient), bit for bit against a second run for everything, and within the float64 bounds of tests/sa_ref.py.
-Then SALayer and SparseBasicBlock(with_sa=True) of both backbones on one shared 300-site case."""
+Then SALayer, SparseBasicBlock(with_sa=True) under both backbones' names and the block with squeeze-excite alone on one
+shared 300-site case."""
 from functools import partial
 
 import numpy as np
@@ -214,6 +215,38 @@ def test_basic_block_with_sa(dev, layer_case, backbone, mode):
         g_err = float((got[n].cpu().double() - want_g).abs().max())
         print(f"  d {n}: max error {g_err:.3e}")
         assert g_err < 1e-4 * max(1.0, float(want_g.abs().max())), n
+
+
+def test_basic_block_with_se_alone_keeps_the_separate_passes_in_eval(dev, layer_case):
+    """SparseBasicBlock(32, 32, with_se=True) in eval() under no_grad is, bit for bit, the sequence assembled from its own
+    modules: conv1, bn1 + ReLU, conv2, bn2 as passes of their own (no BatchNorm folded into the convs, although both convs
+    could take it), squeeze-excite, + identity, ReLU -- what SparseUnet's conv3 / conv4 tails compute in inference."""
+    from openseg3d_amd import ops, segformer
+    case = layer_case
+    torch.manual_seed(11)
+    norm = partial(torch.nn.BatchNorm1d, eps=1e-3, momentum=0.01)
+    block = segformer.SparseBasicBlock(C_LAYER, C_LAYER, norm, torch.nn.ReLU(), indice_key="subm1", with_se=True).to(dev)
+    assert block.se is not None and block.sa is None
+    with torch.no_grad():
+        for bn in (block.bn1, block.bn2):
+            bn.running_mean.normal_(0, 0.1)
+            bn.running_var.uniform_(0.5, 1.5)
+            bn.weight.uniform_(0.5, 1.5)
+            bn.bias.normal_(0, 0.1)
+    x = torch.from_numpy(case["x"]).to(dev)
+    block.eval()
+    with torch.no_grad():
+        xt = _tensor(case, dev, x)
+        assert block.conv1.fusable_with(block.bn1, xt) and block.conv2.fusable_with(block.bn2, xt)
+        out = block(xt).features
+        y = block.conv1(xt)
+        y = y.replace_feature(ops.batch_norm_act(y.features, block.bn1, relu=True))
+        y = block.conv2(y)
+        f = ops.batch_norm_act(y.features, block.bn2, relu=False)
+        f = block.se(f, y.indices[:, 0], y.level.sample_offsets())
+        want = torch.relu(f + x)
+    print(f"SE-only eval: max difference {float((out - want).abs().max()):.3e}")
+    assert torch.equal(out, want)
 
 
 @pytest.mark.parametrize("backbone", ["segformer", "spnet"])

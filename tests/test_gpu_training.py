@@ -453,7 +453,7 @@ def test_side_stream_weight_gradients_keep_autograd_semantics(monkeypatch):
 
 
 def test_batch_prepared_on_the_pipeline_stream_gives_the_same_logits():
-    """bench.py's input pipeline: batch i+1 is voxelized, collated and planned (Segformer.prepare_batch) on its own stream
+    """bench.py's input pipeline: batch i+1 is voxelized, collated and planned (Segmentor.prepare_batch) on its own stream
     while batch i runs.  A batch built that way -- beside a forward in flight on the main stream, then handed over by an
     event -- gives bit-identical logits to the same scene built and run on one stream; and a model run twice on a
     prepared batch does not rebuild the plan."""
@@ -609,7 +609,7 @@ def test_two_gpus_rccl_all_reduce():
 
 def test_eval_forward_replays_from_a_hip_graph():
     """Every C-ABI entry point is sync-free and allocation-free (include/seg3d_hip.h), and a batch can carry its index plan
-    (Segformer.prepare_batch: all host read-backs happen there): the eval forward of a prepared batch -- point encoder,
+    (Segmentor.prepare_batch: all host read-backs happen there): the eval forward of a prepared batch -- point encoder,
     VFE, 20 sparse convs, 18 window-attention layers, gathers, classifier: ~400 launches -- is captured into ONE hipGraph
     and replayed.  The replay must reproduce the eager logits bit for bit, and again after the input rows are overwritten
     in place with another scene's features (same geometry): the graph reads the buffers, not values frozen at capture."""

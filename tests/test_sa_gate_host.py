@@ -142,7 +142,13 @@ def test_construction_and_state_dict_keys():
     sa = segformer.SALayer(32, indice_key="subm1")
     assert {k: tuple(v.shape) for k, v in sa.state_dict().items()} == {"conv.weight": (1, 3, 3, 3, 32)}
     assert spnet.SALayer is segformer.SALayer
+    assert spnet.SparseBasicBlock is segformer.SparseBasicBlock and spnet.UpBlock is segformer.UpBlock
     norm = partial(torch.nn.BatchNorm1d, eps=1e-3, momentum=0.01)
+    # the two reference classes order indice_key and with_se differently: the options are keyword-only
+    with pytest.raises(TypeError):
+        segformer.SparseBasicBlock(32, 32, norm, torch.nn.ReLU(), "subm1")
+    with pytest.raises(TypeError):
+        segformer.SparseBasicBlock(32, 32, norm, torch.nn.ReLU(), True)
     for mod in (segformer, spnet):
         block = mod.SparseBasicBlock(32, 32, norm, torch.nn.ReLU(), indice_key="subm1", with_sa=True)
         assert tuple(block.state_dict()["sa.conv.weight"].shape) == (1, 3, 3, 3, 32)
